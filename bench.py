@@ -12,10 +12,16 @@ Workload: BASELINE.json configs[2] -- "Full hg38, 50M-read synthetic STAR concor
 generator config C3 (50.8 M concordant records, zlib level 6), the largest single-GPU configuration.
 `--workload C5` = configs[4], the dense-graph stress (-w 1 -a 50, >= 1e5 small components): reports components/s.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) reads the input build() left in build/bench_data (or generates it), warms up, times the
+K steps and prints the result line: `value`, `ms_per_step` and what the timed steps' own timers and counts say.  `--full` adds
+everything else below (staged_value, resident_pass, roofline, cold_cli, cpu_baseline, dense, bwa), as every run did before.
+`--dump-outputs DIR` writes what the last timed step computed (the `_sv.txt` columns and the component sizes) as DIR/<name>.npy.
+
   value            alignments/s of the step FROM THE BAM FILE (page cache warm, nothing kept from earlier reads: sq_drop_file_cache before
                    every step): the file streamed into HBM (pread -> page-locked buffers -> copies running ahead of the token pass), its
                    BGZF headers walked, BGZF/BAM decode, graph, ordering, SV calls, `_sv.txt` written -- BASELINE.json's "BAM -> _sv.txt".
                    These are the K timed steps of the contract.
+  (--full only:)
   staged_value     the same step with the COMPRESSED BAM BYTES ALREADY IN HBM (sq_stage_bam) -- the bench contract's "inputs already
                    resident in HBM" reading; reported beside `value`, never as it
   cold_cli         fresh `build/squid -b -c -o` processes (wall clock from exec to exit, page cache warm): one started the moment this
@@ -25,9 +31,9 @@ generator config C3 (50.8 M concordant records, zlib level 6), the largest singl
                    pass / 8 TB/s; the per-kernel table sits beside it
   cpu_baseline     the CPU oracle (a port of the reference, 1 core, pinned) on THE BENCH'S OWN BAM files; its _sv.txt is
                    compared with the timed steps' (`--cpu-sample-records N` times it on a smaller sample instead)
-  dense            (default invocation, N = 1) BASELINE.json configs[4] -- C5, 100 M records, -w 1 -a 50 -- as a sub-record: from-file
+  dense            (--full, N = 1) BASELINE.json configs[4] -- C5, 100 M records, -w 1 -a 50 -- as a sub-record: from-file
                    steps, resident pass, components/s, `_sv.txt` of a 1 M-record sample of it compared with the CPU oracle
-  bwa              (default invocation, N = 1) `squid --bwa` on the C3 sample in the shape `bwa mem` writes, as a
+  bwa              (--full, N = 1) `squid --bwa` on the C3 sample in the shape `bwa mem` writes, as a
                    sub-record: from-file steps, `_sv.txt` of a 1 M-record sample of it compared with the CPU oracle
 
 N > 1 (`--gpus N`; the script launches its own ranks through torch.distributed.run when WORLD_SIZE is not set):
@@ -74,10 +80,17 @@ WORKLOADS = {
     "C5g": "dense-graph stress (-w 1 -a 50), round-2 shape: junctions at inner exons, the segments chain into one giant component",
 }
 DENSE = {"min_edge_weight": 1, "max_allowed_degree": 50}  # -w 1 -a 50
+INPUT_DIR = BUILD / "bench_data"  # (git-ignored) inputs build() generates on a machine with a GPU (prepare_inputs); only read by runs
+DEFAULT_WORKDIR = Path(tempfile.gettempdir()) / f"squid_bench_{os.getuid()}"  # what a run writes, and inputs INPUT_DIR does not hold
+DUMP_MAX_ELEMENTS = 500_000  # per dumped array: 14 float64 arrays of this length stay below 64 MB
 
 
 def synth(config: str, seed: int, outdir: Path, records: int | None = None, level: int | None = None, tsv: int | None = None, support: str | None = None, bwa: bool = False) -> Path:
-    pre = outdir / (f"{config}{'bwa' if bwa else ''}_s{seed}" + (f"_r{records}" if records else "") + (f"_t{tsv}" if tsv else "") + (f"_l{level}" if level is not None else "") + (f"_u{support.replace(',', '-')}" if support else ""))
+    name = f"{config}{'bwa' if bwa else ''}_s{seed}" + (f"_r{records}" if records else "") + (f"_t{tsv}" if tsv else "") + (f"_l{level}" if level is not None else "") + (f"_u{support.replace(',', '-')}" if support else "")
+    prepared = INPUT_DIR / name  # (made by build(), possibly as another user: read it, never write there)
+    if all(os.access(f"{prepared}{ext}", os.R_OK) for ext in ((".bam",) if bwa else (".bam", ".chim.bam"))):
+        return prepared
+    pre = outdir / name
     if not Path(f"{pre}.bam").exists():
         tmp = Path(f"{pre}.tmp{os.getpid()}")
         cmd = [str(BUILD / "gen_synth_bam"), "--config", config, "--seed", str(seed), "--out", str(tmp), "--threads", str(max(1, os.cpu_count() or 8))]
@@ -96,6 +109,47 @@ def synth(config: str, seed: int, outdir: Path, records: int | None = None, leve
             if os.path.exists(f"{tmp}{ext}"):  # (--bwa: one file, no chimeric BAM)
                 os.replace(f"{tmp}{ext}", f"{pre}{ext}")
     return pre
+
+
+def prepare_inputs() -> Path:
+    """generate the default workload's BAM files into INPUT_DIR, where every run looks first (C3, seed of rank 0): build() calls this on
+    a machine with a GPU, so that the first run does not spend its time in the generator (5.9 GB of BGZF at zlib level 6)"""
+    INPUT_DIR.mkdir(parents=True, exist_ok=True)
+    return synth("C3", 20180003, INPUT_DIR)
+
+
+def dump_outputs(outdir: Path, sv_text: str, ref_names: list, comp_sizes) -> None:
+    """what the last timed step computed, as float64 arrays: the columns of its `_sv.txt` (chromosomes as indices into the BAM
+    header, strands as 1 = '-') and the number of nodes of every ordered component.  An array longer than DUMP_MAX_ELEMENTS is
+    replaced by a fixed, seeded sample of its entries, with the sampled positions beside it (<name>_index.npy)."""
+    import numpy as np
+
+    outdir.mkdir(parents=True, exist_ok=True)
+    names = ["chrom1", "start1", "end1", "chrom2", "start2", "end2", "score", "strand1_minus", "strand2_minus", "num_concordantfrag_bp1", "num_concordantfrag_bp2"]
+    ref_index = {n: i for i, n in enumerate(ref_names)}
+    rows = []
+    for line in sv_text.splitlines()[1:]:
+        f = line.split("\t")
+        rows.append((ref_index[f[0]], int(f[1]), int(f[2]), ref_index[f[3]], int(f[4]), int(f[5]), int(f[7]), f[8] == "-", f[9] == "-", int(f[10]), int(f[11])))
+    sv = np.array(rows, dtype=np.float64).reshape(-1, len(names))
+    comp = np.asarray(comp_sizes if comp_sizes is not None else [], dtype=np.float64)
+
+    def pick(n: int, seed: int):
+        if n <= DUMP_MAX_ELEMENTS:
+            return None
+        return np.sort(np.random.default_rng(seed).choice(n, DUMP_MAX_ELEMENTS, replace=False))
+
+    idx = pick(len(sv), 20180001)
+    if idx is not None:
+        sv = sv[idx]
+        np.save(outdir / "sv_index.npy", idx.astype(np.float64))
+    for k, name in enumerate(names):
+        np.save(outdir / f"sv_{name}.npy", np.ascontiguousarray(sv[:, k]))
+    idx = pick(len(comp), 20180002)
+    if idx is not None:
+        comp = comp[idx]
+        np.save(outdir / "component_sizes_index.npy", idx.astype(np.float64))
+    np.save(outdir / "component_sizes.npy", comp)
 
 
 def cpu_model() -> str:
@@ -348,18 +402,21 @@ def main() -> None:
     ap.add_argument("--records", type=int, default=None, help="override the record count of the workload (generator --records)")
     ap.add_argument("--tsv", type=int, default=None, help="override the number of planted junctions (generator --tsv)")
     ap.add_argument("--shard", choices=["sample", "chromosome"], default="chromosome", help="what the ranks of a multi-GPU run divide (see the module docstring)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cold-cli", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle")
+    ap.add_argument("--no-cold-cli", action="store_true", help="(--full) skip the fresh command-line processes")
     ap.add_argument("--support", default=None, help="chimeric fragments per planted junction, lo,hi (generator --support, default 10,60)")
     ap.add_argument("--cpu-sample-tsv", type=int, default=0, help="planted junctions of that sample (generator --tsv; 0 = as the workload)")
     ap.add_argument("--cpu-sample-records", type=int, default=0, help="time the CPU oracle on a sample of this many records instead of the bench's own BAM (0 = the bench's BAM)")
-    ap.add_argument("--resident-steps", type=int, default=5, help="extra (untimed for `value`) graph passes over resident records, for the per-kernel roofline figures")
+    ap.add_argument("--resident-steps", type=int, default=5, help="(--full) extra (untimed for `value`) graph passes over resident records, for the per-kernel roofline figures")
     ap.add_argument("--level", type=int, default=None, help="zlib level of the synthetic BAM (generator --level; 0 = stored blocks: SURVEY.md 8(d)'s variant that separates inflate from parse cost)")
-    ap.add_argument("--staged-steps", type=int, default=8, help="steps of the staged variant (compressed BAM bytes already in HBM) behind the timed from-file steps; at most --steps")
-    ap.add_argument("--no-dense", action="store_true", help="skip the dense-config sub-record (C5, BASELINE.json configs[4]) that the default invocation appends")
-    ap.add_argument("--no-bwa", action="store_true", help="skip the --bwa sub-record (the C3 sample in the shape `bwa mem` writes, read in --bwa mode) that the default invocation appends")
+    ap.add_argument("--staged-steps", type=int, default=8, help="(--full) steps of the staged variant (compressed BAM bytes already in HBM) behind the timed from-file steps; at most --steps")
+    ap.add_argument("--no-dense", action="store_true", help="skip the dense-config sub-record (C5, BASELINE.json configs[4]) that --full appends")
+    ap.add_argument("--no-bwa", action="store_true", help="skip the --bwa sub-record (the C3 sample in the shape `bwa mem` writes, read in --bwa mode) that --full appends")
     ap.add_argument("--dense-records", type=int, default=None, help="record count of the dense sub-record (generator --records; default: the config's 100 M)")
-    ap.add_argument("--workdir", default=None)
+    ap.add_argument("--workdir", default=None, help="where the run writes its files, and generates and keeps the synthetic BAM files that build/bench_data does not hold (default: squid_bench_<uid> in the temporary directory)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need (staged steps, resident passes and "
+                    "roofline, cold command line, CPU oracle, dense and --bwa sub-records); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (_sv.txt columns, component sizes) as DIR/<name>.npy")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -400,7 +457,7 @@ def main() -> None:
     # cold command line, one sample per process, runs without it)
     squid_amd.keep_host_memory()
 
-    work = Path(a.workdir) if a.workdir else Path(tempfile.gettempdir()) / "squid_bench"
+    work = Path(a.workdir) if a.workdir else DEFAULT_WORKDIR
     work.mkdir(parents=True, exist_ok=True)
     srank = 0 if sharded else rank  # a sharded run works on ONE sample
     cfgnum = int(a.workload[1:2]) if a.workload[1:2].isdigit() else 7
@@ -495,15 +552,19 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     note(f"{a.steps} timed steps from the file: {elapsed / a.steps * 1e3:.1f} ms per step")
     text = sv_path.read_text() if (rank == 0 or not sharded) else ""
+    step_comp_sizes = comp_sizes  # (the resident passes of --full overwrite comp_sizes)
     if len(set(digests)) != 1:
         raise SystemExit(f"the timed steps wrote different _sv.txt files: {sorted(set(digests))}")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(Path(a.dump_outputs), text, ctx.ref_names, step_comp_sizes)
+        note(f"outputs of the last timed step written to {a.dump_outputs}")
     e2e: dict[str, dict] = {k: dict(v) for k, v in ctx.timing().items()}
     counts = ctx.counts()
     n_aln = counts["n_concordant"] + (counts["n_chimeric_records"] if (not sharded or rank == 0) else 0)
     n_conc, n_blk = counts["n_concordant"], counts["n_blocks"]
 
     # ---- the same step with the compressed BAM bytes already in HBM (the contract's "inputs resident in HBM" reading; not `value`)
-    n_staged_steps = max(1, min(a.steps, a.staged_steps)) if world == 1 else 0  # (single GPU only: a rank of a sharded run reads its own byte range of the file)
+    n_staged_steps = max(1, min(a.steps, a.staged_steps)) if (world == 1 and a.full) else 0  # (single GPU only: a rank of a sharded run reads its own byte range of the file)
     t_staged = 0.0
     if n_staged_steps:
         ctx.stage_bam(bam)
@@ -519,16 +580,20 @@ def main() -> None:
         note(f"staged steps: {t_staged * 1e3:.1f} ms per step")
 
     # ---- graph pass alone over the resident records: per-kernel figures for the roofline
-    ctx.timing_accumulate(True)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(a.resident_steps):
-        ctx.reset()
-        graph_pass()
-    barrier()
-    t_res = (time.perf_counter() - t0) / max(1, a.resident_steps)
-    note(f"resident passes: {t_res * 1e3:.1f} ms per pass")
-    agg: dict[str, dict] = {k: dict(v) for k, v in ctx.timing().items()}
+    n_resident = a.resident_steps if a.full else 0
+    agg: dict[str, dict] = {}
+    t_res = 0.0
+    if n_resident:
+        ctx.timing_accumulate(True)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(n_resident):
+            ctx.reset()
+            graph_pass()
+        barrier()
+        t_res = (time.perf_counter() - t0) / n_resident
+        note(f"resident passes: {t_res * 1e3:.1f} ms per pass")
+        agg = {k: dict(v) for k, v in ctx.timing().items()}
     settle_s = float(os.environ.get("BENCH_COLD_SETTLE_S", "4"))
 
     from squid_amd.dist import reduce_timing
@@ -548,43 +613,59 @@ def main() -> None:
             dist.destroy_process_group()
         return
 
-    n_passes = a.steps + a.warmup + (n_staged_steps + 1 if n_staged_steps else 0) + a.resident_steps
+    n_passes = a.steps + a.warmup + (n_staged_steps + 1 if n_staged_steps else 0) + n_resident
     x_all = list(x_stats)
     if sharded:
         n_, b_ = ctx.exchange_stats()
         x_all = [x_stats[0] + n_, x_stats[1] + b_]
     value = total_aln * a.steps / elapsed
-    R = max(1, a.resident_steps)
-    # the record-streaming kernels of the graph pass (K1-K5, K10), by accumulated HIP-event time on the library stream
-    gk = {k: v for k, v in agg.items() if k.startswith(GPU_KERNELS_PREFIX) and v["bytes"] > 0 and k not in INGEST_KERNELS and k not in SMALL_GRAPH_KERNELS}
-    gk_all = dict(gk)
-    for name in ("k_edges", "k_depth2"):  # (pass 2 of the edge stage; the general depth sweep over the tiles k_pass2w left: their time counts, their bytes are not priced)
-        if name in agg and name not in gk_all:
-            gk_all[name] = agg[name]
-    dom = max(gk, key=lambda k: gk[k]["ms"])
-    d = gk[dom]
-    gpu_ms = sum(v["ms"] for v in gk_all.values()) / R
-    scan_bytes = sum(v["bytes"] for v in gk.values()) / R
+    R = max(1, n_resident)
     bbar = total_blk / max(1.0, total_conc)
-    sec8d_bytes = total_conc / world * (80.0 + 24.0 * bbar) if sharded else n_conc * (80.0 + 24.0 * bbar)
-    achieved = sec8d_bytes / (gpu_ms * 1e-3) / 1e9 if gpu_ms > 0 else 0.0
-    # the same figure with the small helpers of K5 / K10 that SURVEY.md 8(d)'s sum also names (bucket and fold kernels, the breakpoint-cursor walks, the hash
-    # compaction: launches that touch kilobytes -- their time counts, they have no bytes of their own)
-    helpers = {k: v for k, v in agg.items() if k in ("k_hash_compact", "k_node_buckets", "k_bp_walk", "k_bp_key_prefix") and k not in gk_all}
-    helper_ms = sum(v["ms"] for v in helpers.values()) / R
-    achieved_h = sec8d_bytes / ((gpu_ms + helper_ms) * 1e-3) / 1e9 if gpu_ms > 0 else 0.0
-    traffic = None
-    tfile = ROOT / "profiles" / "pmc_traffic.json"  # written by tools/profile_pmc.sh from the rocprofv3 --pmc passes
-    per_kernel_traffic = {}
-    if tfile.exists():
-        try:
-            tj = json.loads(tfile.read_text())
-            if tj.get("_workload") == a.workload and not a.records and world == 1:  # the counters were collected on this workload
-                per_kernel_traffic = {k: (tj.get(k) or {}).get("hbm_bytes_per_launch") for k in gk_all}
-                if all(per_kernel_traffic.get(k) is not None for k in gk):
-                    traffic = sum(per_kernel_traffic[k] * (gk[k]["launches"] / R) for k in gk)  # HBM bytes of the record-streaming kernels of one pass
-        except Exception:
-            traffic = None
+
+    def roofline() -> dict:
+        # the record-streaming kernels of the graph pass (K1-K5, K10), by accumulated HIP-event time on the library stream
+        gk = {k: v for k, v in agg.items() if k.startswith(GPU_KERNELS_PREFIX) and v["bytes"] > 0 and k not in INGEST_KERNELS and k not in SMALL_GRAPH_KERNELS}
+        gk_all = dict(gk)
+        for name in ("k_edges", "k_depth2"):  # (pass 2 of the edge stage; the general depth sweep over the tiles k_pass2w left: their time counts, their bytes are not priced)
+            if name in agg and name not in gk_all:
+                gk_all[name] = agg[name]
+        dom = max(gk, key=lambda k: gk[k]["ms"])
+        d = gk[dom]
+        gpu_ms = sum(v["ms"] for v in gk_all.values()) / R
+        scan_bytes = sum(v["bytes"] for v in gk.values()) / R
+        sec8d_bytes = total_conc / world * (80.0 + 24.0 * bbar) if sharded else n_conc * (80.0 + 24.0 * bbar)
+        achieved = sec8d_bytes / (gpu_ms * 1e-3) / 1e9 if gpu_ms > 0 else 0.0
+        # the same figure with the small helpers of K5 / K10 that SURVEY.md 8(d)'s sum also names (bucket and fold kernels, the breakpoint-cursor walks, the hash
+        # compaction: launches that touch kilobytes -- their time counts, they have no bytes of their own)
+        helpers = {k: v for k, v in agg.items() if k in ("k_hash_compact", "k_node_buckets", "k_bp_walk", "k_bp_key_prefix") and k not in gk_all}
+        helper_ms = sum(v["ms"] for v in helpers.values()) / R
+        achieved_h = sec8d_bytes / ((gpu_ms + helper_ms) * 1e-3) / 1e9 if gpu_ms > 0 else 0.0
+        traffic = None
+        tfile = ROOT / "profiles" / "pmc_traffic.json"  # written by tools/profile_pmc.sh from the rocprofv3 --pmc passes
+        per_kernel_traffic = {}
+        if tfile.exists():
+            try:
+                tj = json.loads(tfile.read_text())
+                if tj.get("_workload") == a.workload and not a.records and world == 1:  # the counters were collected on this workload
+                    per_kernel_traffic = {k: (tj.get(k) or {}).get("hbm_bytes_per_launch") for k in gk_all}
+                    if all(per_kernel_traffic.get(k) is not None for k in gk):
+                        traffic = sum(per_kernel_traffic[k] * (gk[k]["launches"] / R) for k in gk)  # HBM bytes of the record-streaming kernels of one pass
+            except Exception:
+                traffic = None
+        return {"bound": "hbm", "kernel": "record-streaming kernels of one graph pass: " + " + ".join(sorted(gk_all, key=lambda k: -gk_all[k]["ms"])),
+                "definition": "SURVEY.md 8(d): N_c * (80 + 24 * blocks per record) algorithmic bytes / summed HIP-event time of those kernels",
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                "bytes_per_launch": sec8d_bytes, "us_per_launch": gpu_ms * 1e3,
+                "sum_of_kernel_bytes_per_pass": scan_bytes, "kernel_bytes_over_algorithmic": scan_bytes / sec8d_bytes if sec8d_bytes else None,
+                "frac_of_measured_copy_peak_6290": achieved / 6290.0,
+                "frac_incl_helpers": achieved_h / HBM_PEAK_GBS, "helper_us_per_pass": {k: round(v["ms"] / R * 1e3, 1) for k, v in sorted(helpers.items(), key=lambda kv: -kv[1]["ms"])},
+                "dominant_kernel": {"name": dom, "us": d["ms"] / d["launches"] * 1e3, "bytes_per_launch": d["bytes"] / d["launches"], "GBs": d["bytes"] / d["ms"] / 1e6,
+                                    "frac": d["bytes"] / d["ms"] / 1e6 / HBM_PEAK_GBS, "traffic": per_kernel_traffic.get(dom)},
+                # every record-streaming kernel of the pass: us per launch, achieved GB/s of its own bytes, fraction of the HBM peak
+                "record_kernels": {k: {"us": round(v["ms"] / v["launches"] * 1e3, 1), "launches_per_pass": round(v["launches"] / R, 2), "GBs": round(v["bytes"] / v["ms"] / 1e6, 1),
+                                       "frac": round(v["bytes"] / v["ms"] / 1e6 / HBM_PEAK_GBS, 3)} for k, v in sorted(gk_all.items(), key=lambda kv: -kv[1]["ms"]) if v["ms"] > 0},
+                "note": "the BGZF inflate kernels dominate the step's GPU time but are latency-bound bit-serial decoders, not HBM streams: listed under ingest_kernels"}
+
     ing = {k: e2e[k] for k in INGEST_KERNELS if k in e2e and e2e[k]["ms"] > 0}
     out = {
         "metric": "paired-end alignments/sec BAM->_sv.txt (from the BAM files in the page cache: file read, host->device copy, BGZF/BAM decode, graph, ordering, SV calls, _sv.txt written; bit-exact SV calls vs CPU oracle)",
@@ -597,52 +678,44 @@ def main() -> None:
                    "parallelism": ("one sample sharded by chromosome over %d ranks, %.1f all-gathers (%.0f payload bytes) per step inside the library (sq_exchange over %s)" % (world, x_all[0] / max(1, n_passes), x_all[1] / max(1, n_passes), "RCCL" if dist.get_backend() == "nccl" else dist.get_backend()) if sharded else "1 sample per GPU, no collective") if world > 1 else "single GPU",
                    "step": "chimeric BAM decode (host) + concordant BAM decode on the GPU (BGZF inflate, record boundaries, record parse) + graph + ordering + SV calls + _sv.txt written; every step reads the BAM file again (page cache warm; mapping and BGZF block index dropped before the step, the compressed bytes streamed to HBM inside it)"},
         "sv_sha256": digests[0], "sv_rows": text.count("\n") - 1, "steps_identical": True,
-        "roofline": {"bound": "hbm", "kernel": "record-streaming kernels of one graph pass: " + " + ".join(sorted(gk_all, key=lambda k: -gk_all[k]["ms"])),
-                     "definition": "SURVEY.md 8(d): N_c * (80 + 24 * blocks per record) algorithmic bytes / summed HIP-event time of those kernels",
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "bytes_per_launch": sec8d_bytes, "us_per_launch": gpu_ms * 1e3,
-                     "sum_of_kernel_bytes_per_pass": scan_bytes, "kernel_bytes_over_algorithmic": scan_bytes / sec8d_bytes if sec8d_bytes else None,
-                     "frac_of_measured_copy_peak_6290": achieved / 6290.0,
-                     "frac_incl_helpers": achieved_h / HBM_PEAK_GBS, "helper_us_per_pass": {k: round(v["ms"] / R * 1e3, 1) for k, v in sorted(helpers.items(), key=lambda kv: -kv[1]["ms"])},
-                     "dominant_kernel": {"name": dom, "us": d["ms"] / d["launches"] * 1e3, "bytes_per_launch": d["bytes"] / d["launches"], "GBs": d["bytes"] / d["ms"] / 1e6,
-                                         "frac": d["bytes"] / d["ms"] / 1e6 / HBM_PEAK_GBS, "traffic": per_kernel_traffic.get(dom)},
-                     # every record-streaming kernel of the pass: us per launch, achieved GB/s of its own bytes, fraction of the HBM peak
-                     "record_kernels": {k: {"us": round(v["ms"] / v["launches"] * 1e3, 1), "launches_per_pass": round(v["launches"] / R, 2), "GBs": round(v["bytes"] / v["ms"] / 1e6, 1),
-                                            "frac": round(v["bytes"] / v["ms"] / 1e6 / HBM_PEAK_GBS, 3)} for k, v in sorted(gk_all.items(), key=lambda kv: -kv[1]["ms"]) if v["ms"] > 0},
-                     "note": "the BGZF inflate kernels dominate the step's GPU time but are latency-bound bit-serial decoders, not HBM streams: listed under ingest_kernels"},
         # BGZF reader: its kernels run on several streams and overlap.  busy_ms_per_step = time during which at least one launch of the
         # name was running; us_per_launch = average duration of one launch (what rocprofv3 --stats reports per kernel)
         "ingest_kernels": {k: {"launches_per_step": round(v["launches"] / a.steps, 1), "us_per_launch": round(v["ms"] / v["launches"] * 1e3, 1), "busy_ms_per_step": round(v["busy_ms"] / a.steps, 3),
                                "GBs_over_busy_time": round(v["bytes"] / max(v["busy_ms"], 1e-9) / 1e6, 1)} for k, v in ing.items()},
         "ms_each": [round(x, 1) for x in file_ms],
-        "staged_value": total_aln / t_staged if t_staged > 0 else None, "staged_ms_per_step": t_staged * 1e3 if t_staged > 0 else None, "staged_steps": n_staged_steps,
-        "staged_note": "the same step with the compressed BAM bytes already in HBM (sq_stage_bam): the bench contract's 'inputs resident in HBM' reading -- no file read, no host->device copy of the 5.9 GB inside the step; reported beside `value`, which is the PCIe-inclusive figure BASELINE.json's metric (BAM -> _sv.txt) asks for",
-        "resident_pass_value": total_aln / t_res, "resident_pass_ms": t_res * 1e3,
         "stage_ms_per_step": {k: round(v["ms"] / a.steps, 4) for k, v in sorted(e2e.items(), key=lambda kv: -kv[1]["ms"]) if k not in INGEST_KERNELS and (os.environ.get("BENCH_ALL_STAGES") or v["ms"] / a.steps >= 0.5)},
-        "resident_stage_ms": {k: round(v["ms"] / R, 4) for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])[:(None if os.environ.get("BENCH_ALL_STAGES") else 18)]},
         "synth_s": round(t_gen, 1),
     }
+    if n_resident:  # (--full)
+        out["roofline"] = roofline()
+        out.update({"resident_pass_value": total_aln / t_res, "resident_pass_ms": t_res * 1e3,
+                    "resident_stage_ms": {k: round(v["ms"] / R, 4) for k, v in sorted(agg.items(), key=lambda kv: -kv[1]["ms"])[:(None if os.environ.get("BENCH_ALL_STAGES") else 18)]}})
+    if a.full:
+        out.update({"staged_value": total_aln / t_staged if t_staged > 0 else None, "staged_ms_per_step": t_staged * 1e3 if t_staged > 0 else None, "staged_steps": n_staged_steps,
+                    "staged_note": "the same step with the compressed BAM bytes already in HBM (sq_stage_bam): the bench contract's 'inputs resident in HBM' reading -- no file read, no host->device copy of the 5.9 GB inside the step; reported beside `value`, which is the PCIe-inclusive figure BASELINE.json's metric (BAM -> _sv.txt) asks for"})
     if ingest_per_rank:
         out["ingest_per_rank"] = ingest_per_rank
     if comp_sizes is not None and len(comp_sizes):
         import numpy as np
 
-        # K9: components per second of the ordering stage and of the whole step, sizes as a histogram
-        order_ms = agg.get("wall_order", {}).get("ms", 0.0) / R
+        # K9: components per second of the whole step (and, with --full, of the ordering stage), sizes as a histogram
         hist = np.bincount(np.minimum(comp_sizes, 20))
         out["components"] = {"n": int(len(comp_sizes)), "n_with_2_or_more_nodes": int((comp_sizes >= 2).sum()), "largest": int(comp_sizes.max()),
                              "size_histogram": {("20+" if s == 20 else str(s)): int(c) for s, c in enumerate(hist) if c},
-                             "ccs_per_s_ordering_stage": len(comp_sizes) / (order_ms * 1e-3) if order_ms > 0 else None,
-                             "ccs_per_s_whole_step": len(comp_sizes) * a.steps / elapsed, "ordering_ms_per_pass": order_ms,
+                             "ccs_per_s_whole_step": len(comp_sizes) * a.steps / elapsed,
                              "n_components_ge20": int((comp_sizes >= 20).sum()), "n_order_unsolved": int(counts["n_order_unsolved"])}
+        if n_resident:
+            order_ms = agg.get("wall_order", {}).get("ms", 0.0) / R
+            out["components"]["ccs_per_s_ordering_stage"] = len(comp_sizes) / (order_ms * 1e-3) if order_ms > 0 else None
+            out["components"]["ordering_ms_per_pass"] = order_ms
     close_context(ctx)
-    if not a.no_cold_cli and world == 1:
+    if a.full and not a.no_cold_cli and world == 1:
         # what a user runs once: a fresh process, nothing staged, nothing cached inside the process (the page cache is warm).  Twice:
         # the moment this process has released its ~40 GB of device memory (`immediate`: the driver wipes released VRAM, and a process that
         # starts meanwhile waits for the wipe in its first device allocations -- 4 GiB hipMalloc 0.2 ms on an idle GPU, 150-240 ms right behind
         # a release) and settle_s seconds after that one (a GPU left alone, what a user's first run finds)
         out["cold_cli"] = cold_cli(bam, chim, work / "cold_cli", cli_flags, text, total_aln, settle_s, note)
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         # CPU oracle (a port of the reference, 1 thread, pinned) timed on this box: on the bench's own BAM files (its _sv.txt must equal
         # the timed steps'), or with --cpu-sample-records on a smaller sample of the same workload that the GPU path then runs too
         pin = ["taskset", "-c", "0"] if shutil.which("taskset") else []
@@ -675,9 +748,9 @@ def main() -> None:
                                "unsolved": int(ostats["too_large"])}
         if "components" in out and not a.cpu_sample_records:
             out["components"]["ambiguous"] = int(ostats["ambiguous"])
-    if world == 1 and a.workload == "C3" and not a.records and not a.no_dense:
+    if a.full and world == 1 and a.workload == "C3" and not a.records and not a.no_dense:
         out["dense"] = dense_record(work, local_rank, note, records=a.dense_records)
-    if world == 1 and a.workload == "C3" and not a.records and not a.no_bwa:
+    if a.full and world == 1 and a.workload == "C3" and not a.records and not a.no_bwa:
         out["bwa"] = bwa_record(work, local_rank, note)
     if dist:
         dist.destroy_process_group()
