@@ -161,6 +161,15 @@ int sq_graph_view(sq_ctx* c, int32_t stage, sq_graph* g);
  * nodes and edges on a dense sample, made for inspection and the parity tests -- the result does not need them); sq_graph_view then only
  * answers for stage 0.  Default: kept.  `build/squid` and bench.py switch them off. */
 int sq_keep_stage_graphs(sq_ctx* c, int32_t on);
+/* on != 0: the next sq_build_graph (STAR mode) computes the chimeric raw edges (RawEdgesChim, src/SegmentGraph.cpp:1394-1555) on the device and
+ * sq_call_sv takes the per-edge breakpoint lists (ExactBreakpoint + CountTop, :3019-3081, :51-102) from the device: a fragment table in HBM, made
+ * once per set of chimeric fragments, instead of the host threads' loops over the fragments.  Every result -- stage snapshots, orders,
+ * sq_breakpoints, sq_call_sv -- is identical to the host route's.  Default: off.  May be switched between sq_reset runs on the same context.
+ * A --bwa context (sq_ingest_bwa_file) accepts the call and ignores it: its fragments are rebuilt by RawEdges on the host.  Sharded contexts:
+ * the stage is replicated per rank, on either route.  SQUID_CHIM_STAGES_GPU=1 / =0 in the environment of sq_create forces / forbids the
+ * device route whatever this call says.  A stage with more than 2^20 fragments whose first block has to be resolved in fragment order takes
+ * the host route by itself (sq_get_timing: chim_device_fallback counts these, chim_soft_fragments the fragments resolved in order). */
+int sq_chimeric_on_device(sq_ctx* c, int32_t on);
 
 /* vector<vector<int>> Ordering() -- src/SegmentGraph.cpp:3236-3262: CSR of signed 1-based node ids */
 typedef struct sq_orders {
@@ -301,6 +310,16 @@ int sq_debug_order(sq_ctx* c, int32_t n, int32_t n_edges, const int32_t* edges5,
  * rel5 receives the five n*n relation matrices (0/1 bytes, in that order), perm_pos / perm_readpos the permutations the
  * library's sorts produce with operator< (SegmentGraph.cpp:264) and CompReadPos (ReadRec.cpp:144-145). */
 int sq_debug_blocks(int32_t n, const int32_t* fields7, uint8_t* rel5, int32_t* perm_pos, int32_t* perm_readpos);
+/* tests: both chimeric graph stages (see sq_chimeric_on_device) on caller-supplied tables, by the host route and by the device route, compared.
+ * Takes over the context's fragments, nodes and edges: use a context of its own.  nodes1 / nodes2: n x {chr, pos, len}, the node table of
+ * RawEdgesChim / of ExactBreakpoint; fragment q has the blocks [frag_off[q], frag_off[q + 1]), the first frag_na[q] of them mate a;
+ * frag_tot: n_frag x {total read length of mate a, of mate b}; blocks6: {RefID, RefPos, ReadPos, MatchRef, MatchRead, IsReverse} per block;
+ * edges4: n_edges x {a, b, head_a, head_b} over nodes2, sorted by key.  out8 = {differences (reduced raw edges, trimmed blocks behind
+ * either stage, per-edge breakpoint lists in order, return codes), soft fragments of stage 1 / stage 2 by the host's classification,
+ * the same two as the device counted them, return code of the host route, of the device route (SQ_E_ASSERT: a block outside the node
+ * table), pairs in the largest hit group}.  Returns SQ_OK when both routes could be run. */
+int sq_debug_chim_stages(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
+                         const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8);
 /* tuning: the two BGZF inflate kernels on the first max_blocks blocks of a file, each ALONE on the device, timed with HIP events (the
  * reader overlaps them with everything else).  variant: 2 = the lane-per-block token pass (k_inflate_tok2), else CH * 100 + PB of the
  * wave-per-block pass (k_inflate_spec: 51211, 51210, 25610, 25611, 38411, 102411).  check != 0 compares every block with zlib.

@@ -25,6 +25,7 @@ EXPORTS = [
     "sq_set_shard", "sq_exchange_pack", "sq_exchange_unpack", "sq_get_timing", "sq_timing_accumulate", "sq_reset", "sq_ingest_files", "sq_stage_bam", "sq_clear_records", "sq_set_source", "sq_save_records", "sq_load_records", "sq_get_counts", "sq_debug_download", "sq_debug_bp_support", "sq_debug_order", "sq_debug_blocks", "sq_drop_file_cache",
     "sq_total_order", "sq_set_allgather", "sq_rccl_unique_id", "sq_rccl_init", "sq_rccl_attach", "sq_exchange", "sq_exchange_stats",
     "sq_rccl_available", "sq_rccl_release", "sq_debug_rccl_selftest", "sq_debug_token_bench", "sq_ingest_bwa_file", "sq_junction_sequences", "sq_release_reader_buffers", "sq_keep_host_memory", "sq_keep_stage_graphs",
+    "sq_chimeric_on_device", "sq_debug_chim_stages",
 ]
 
 
@@ -107,6 +108,8 @@ def load_library() -> C.CDLL:
         lib.sq_ingest_files.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32]
         lib.sq_stage_bam.argtypes = [C.c_void_p, C.c_char_p]
         lib.sq_keep_stage_graphs.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_chimeric_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_debug_chim_stages.argtypes = [C.c_void_p, C.c_int32, _P32, C.c_int32, _P32, C.c_int32, _P32, _P32, _P32, _P32, C.c_int32, _P32, C.POINTER(C.c_int64)]
         lib.sq_clear_records.argtypes = [C.c_void_p]
         lib.sq_release_reader_buffers.argtypes = [C.c_void_p]
         lib.sq_set_source.argtypes = [C.c_void_p, C.c_char_p]
@@ -227,6 +230,29 @@ class Context:
     def keep_stage_graphs(self, on: bool = True):
         """sq_keep_stage_graphs: keep (default) or skip the copies of the intermediate graphs that graph(1..5) hands out"""
         self._chk(self.lib.sq_keep_stage_graphs(self.h, 1 if on else 0), "sq_keep_stage_graphs")
+
+    def chimeric_on_device(self, on: bool = True):
+        """sq_chimeric_on_device: the next build_graph computes the chimeric raw edges and the per-edge breakpoint lists on the device (same
+        results; off by default; a --bwa context ignores it)"""
+        self._chk(self.lib.sq_chimeric_on_device(self.h, 1 if on else 0), "sq_chimeric_on_device")
+
+    def debug_chim_stages(self, nodes1, nodes2, frags, edges) -> dict:
+        """sq_debug_chim_stages (tests): both chimeric graph stages on the given tables by the host and by the device route, compared.  nodes: [(chr,
+        pos, len)]; frags: [(blocks of mate a, blocks of mate b, atot, btot)], a block = (refid, refpos, readpos, matchref, matchread, rev); edges:
+        [(a, b, head_a, head_b)] over nodes2, sorted by key.  Uses up the context's fragments and graph."""
+        def arr(v):
+            return (C.c_int32 * max(len(v), 1))(*v)
+
+        off, na, tot, blocks = [0], [], [], []
+        for a, b, atot, btot in frags:
+            for blk in list(a) + list(b):
+                blocks.extend(int(x) for x in blk)
+            off.append(off[-1] + len(a) + len(b)); na.append(len(a)); tot.extend((atot, btot))
+        out = (C.c_int64 * 8)()
+        self._chk(self.lib.sq_debug_chim_stages(self.h, len(nodes1), arr([x for n in nodes1 for x in n]), len(nodes2), arr([x for n in nodes2 for x in n]), len(frags), arr(off), arr(na),
+                                                arr(tot), arr(blocks), len(edges), arr([x for e in edges for x in e]), out), "sq_debug_chim_stages")
+        keys = ("differences", "host_soft_1", "host_soft_2", "device_soft_1", "device_soft_2", "host_rc", "device_rc", "largest_group")
+        return dict(zip(keys, (int(x) for x in out)))
 
     def release_reader_buffers(self):
         """give back the device / page-locked memory the GPU reader keeps between ingests (sq_release_reader_buffers)"""

@@ -160,6 +160,16 @@ static int finish_graph(sq_ctx* c, bool host_filters) {
     c->graph_built = true;
     c->gb.reset();
     // ExactBreakpoint only needs the final graph and the trimmed fragments: start it now, sq_call_sv collects it
+    c->chim_s2_pending = false;
+    if (c->chim_s1_device) {  // the trimmed blocks are in HBM: the stage is queued on the stream behind the graph (sq_chim_stage.inc)
+        bool fb = false;
+        rc = dev_exact_breakpoints_start(c, fb);
+        if (rc) return rc;
+        if (!fb) { c->chim_s2_pending = true; return SQ_OK; }
+        c->timer.add("chim_device_fallback", 0, 0, 1);
+        if ((rc = dev_chim_download_trimmed(c))) return rc;  // (the host stage continues from the blocks as stage 1 left them)
+        c->chim_s1_device = false;
+    }
     c->bp_early = std::make_shared<BPMap>();
     c->bp_future = c->pool->submit([c]() {
         const auto t0 = std::chrono::steady_clock::now();
@@ -178,6 +188,7 @@ static int build_graph_bwa(sq_ctx* c) {
     if (c->shard.on) return fail(c, SQ_E_ARG, "--bwa input is not chromosome-sharded");
     c->graph_built = false; c->ordered = false;
     c->depth_bounds = false; c->depth_ambiguous = false;
+    c->chim_s1_device = false;
     std::vector<Edge> raw;
     int rc = bwa_nodes_and_edges(c, raw);
     if (rc) return rc;
@@ -370,7 +381,18 @@ static int build_graph(sq_ctx* c) {
         // drives the depth and edge kernels over the concordant stream
         c->edges.clear();
         double chim_ms = 0;
-        std::future<int> chim = c->pool->submit([&]() {
+        // (sq_chimeric_on_device: RawEdgesChim as kernels on this stream, in front of the depth stage; a stage with more soft fragments than
+        // the bound comes back and takes the host route below)
+        c->chim_s1_device = false;
+        if (c->chim_dev_on()) {
+            bool fb = false;
+            c->timer.add("chim_device_fallback", 0, 0, 0);
+            rc = dev_chimeric_edges(c, g.raw, fb);
+            if (rc) return rc;
+            if (fb) c->timer.add("chim_device_fallback", 0, 0, 1); else c->chim_s1_device = true;
+        }
+        std::future<int> chim;
+        if (!c->chim_s1_device) chim = c->pool->submit([&]() {
             const auto t0 = std::chrono::steady_clock::now();
             const int r2 = chimeric_edges(c, g.raw);
             chim_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -379,8 +401,8 @@ static int build_graph(sq_ctx* c) {
         std::vector<int32_t> unused;
         rc = dev_node_depth(c, c->nodes, g.n_break, g.sup, g.sl, g.tiny_boundary, g.amb_plus, g.amb_minus, unused);
         int rc_edges = rc ? rc : dev_concordant_edges(c, c->nodes, g.conc);
-        const int rc_chim = chim.get();
-        c->timer.add("host_chimeric_edges", chim_ms);
+        const int rc_chim = chim.valid() ? chim.get() : SQ_OK;
+        if (!c->chim_s1_device) c->timer.add("host_chimeric_edges", chim_ms);
         if (rc_chim) return rc_chim;
         if (rc_edges) return rc_edges;
         g.stage = 4;
@@ -647,7 +669,12 @@ static int call_sv(sq_ctx* c) {
         pk.put_vec(v.diff);
     };
     if (v.stage == 0) {
-        if (c->bp_future.valid()) {
+        if (c->chim_s2_pending || c->chim_s1_device) {  // (chim_s1_device without a pending stage: a second sq_call_sv on the same graph)
+            if (!c->chim_s2_pending) { bool fb = false; rc = dev_exact_breakpoints_start(c, fb); if (rc) return rc; if (fb) return fail(c, SQ_E_ARG, "internal: the breakpoint stage of this graph ran on the device before and does not now"); }
+            c->chim_s2_pending = false;
+            rc = dev_exact_breakpoints_collect(c, bpmap);
+            if (rc) return rc;
+        } else if (c->bp_future.valid()) {
             rc = c->bp_future.get();
             c->timer.add("host_exact_breakpoints", c->bp_early_ms);
             if (rc) return rc;
@@ -818,6 +845,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     sq_ctx* c = new sq_ctx();
     c->P = *p;
     c->pool.reset(new HostPool(host_workers(p->world_size)));
+    if (const char* env = std::getenv("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = std::atoi(env) ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
     *out = c;
@@ -826,6 +854,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
 void sq_destroy(sq_ctx* c) {
     if (!c) return;
     if (c->bp_future.valid()) (void)c->bp_future.get();
+    dev_chim_drop_pending(c);
     exchange_release(c);
     dev_destroy(c);
     delete c;
@@ -1340,6 +1369,7 @@ static int sq_build_graph_impl(sq_ctx* c) {
     if (c->read_len <= 0 && !c->bwa) return fail(c, SQ_E_ARG, "sq_ingest_chimeric first (ReadLen comes from the chimeric BAM)");
     if (c->shard.on != (c->P.world_size > 1)) return fail(c, SQ_E_ARG, "world_size > 1 needs sq_set_shard (and the other way round)");
     if (c->bp_future.valid()) (void)c->bp_future.get();
+    if (!c->gb) { dev_chim_drop_pending(c); c->chim_s2_pending = false; }
     if (!c->gb && !c->timer_keep) c->timer.clear();
     if (!c->gb) c->ablated = false;
     int rc = c->bwa ? build_graph_bwa(c) : build_graph(c);
@@ -1437,6 +1467,8 @@ int sq_timing_accumulate(sq_ctx* c, int32_t keep) {
 int sq_reset(sq_ctx* c) {
     if (!c) return SQ_E_ARG;
     if (c->bp_future.valid()) (void)c->bp_future.get();
+    dev_chim_drop_pending(c);
+    c->chim_s2_pending = false; c->chim_s1_device = false;
     copy_frags(c, c->frags0, c->frags);  // the graph stages trim the chimeric blocks in place, like the reference does
     c->nodes.clear(); c->edges.clear(); c->label.clear();
     c->graph_built = false; c->ordered = false;
@@ -1470,6 +1502,105 @@ int sq_debug_bp_support(sq_ctx* c, int32_t n_bp, const int32_t* chr, const int32
     if (rc) return rc;
     std::copy(cov.begin(), cov.end(), coverage);
     return SQ_OK;
+}
+int sq_chimeric_on_device(sq_ctx* c, int32_t on) {
+    if (!c) return SQ_E_ARG;
+    c->chim_dev_asked = on != 0;  // (a --bwa context keeps the host route: chim_dev_on)
+    return SQ_OK;
+}
+static int sq_debug_chim_stages_impl(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
+                                     const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8) {
+    if (!c || n1 <= 0 || n2 <= 0 || n_frag < 0 || n_edges < 0 || !nodes1 || !nodes2 || !frag_off || !frag_na || !frag_tot || !blocks6 || (n_edges && !edges4) || !out8) return SQ_E_ARG;
+    if (c->bp_future.valid()) (void)c->bp_future.get();
+    dev_chim_drop_pending(c);
+    c->chim_s2_pending = false; c->chim_s1_device = false; c->graph_built = false;
+    std::vector<Frag> F0((size_t)n_frag);
+    for (int32_t q = 0; q < n_frag; ++q) {
+        const int32_t o = frag_off[q], e = frag_off[q + 1], na = frag_na[q];
+        if (o < 0 || e < o || na < 0 || na > e - o) return fail(c, SQ_E_ARG, "sq_debug_chim_stages: malformed fragment table");
+        Frag& f = F0[(size_t)q];
+        f.atot = frag_tot[2 * q]; f.btot = frag_tot[2 * q + 1];
+        for (int32_t k = o; k < e; ++k) {
+            const int32_t* b = blocks6 + 6 * (size_t)k;
+            (k < o + na ? f.a : f.b).push_back(Blk{b[0], b[1], b[2], b[3], b[4], b[5] != 0, k < o + na});
+        }
+    }
+    auto nodes_of = [](int32_t n, const int32_t* v) { std::vector<Node> N((size_t)n); for (int32_t i = 0; i < n; ++i) N[(size_t)i] = Node{v[3 * i], v[3 * i + 1], v[3 * i + 2], 0, 0.0}; return N; };
+    const std::vector<Node> N1 = nodes_of(n1, nodes1), N2 = nodes_of(n2, nodes2);
+    std::vector<Edge> E((size_t)n_edges);
+    for (int32_t i = 0; i < n_edges; ++i) {
+        const int32_t* e = edges4 + 4 * (size_t)i;
+        if (e[0] < 0 || e[1] < e[0] || e[1] >= n2) return fail(c, SQ_E_ARG, "sq_debug_chim_stages: edge outside the node table");
+        E[(size_t)i] = make_edge(e[0], e[2] != 0, e[1], e[3] != 0);
+    }
+    auto same_blocks = [](const std::vector<Frag>& x, const std::vector<Frag>& y) {
+        int64_t bad = 0;
+        for (size_t q = 0; q < x.size(); ++q)
+            for (int mate = 0; mate < 2; ++mate) {
+                const BlkList &p = mate ? x[q].b : x[q].a, &r = mate ? y[q].b : y[q].a;
+                for (size_t k = 0; k < p.size(); ++k) if (p[k].refpos != r[k].refpos || p[k].readpos != r[k].readpos || p[k].matchref != r[k].matchref || p[k].matchread != r[k].matchread) ++bad;
+            }
+        return bad;
+    };
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    // host route
+    c->frags = F0; c->frags0 = F0; ++c->frags_version;
+    c->nodes = N1;
+    out8[1] = chim_stage_soft_count(c, N1, 1);
+    std::vector<Edge> raw_h, red_h, raw_d, red_d;
+    BPMap bp_h, bp_d;
+    std::vector<Frag> h1, h2;
+    int rc_h = chimeric_edges(c, raw_h);
+    if (!rc_h) {
+        reduce_edges(raw_h, red_h);
+        h1 = c->frags;
+        c->nodes = N2; c->edges = E;
+        out8[2] = chim_stage_soft_count(c, N2, 2);
+        rc_h = exact_breakpoints(c, bp_h);
+        h2 = c->frags;
+    }
+    out8[5] = rc_h;
+    c->err.clear();
+    // device route
+    auto soft_seen = [&]() { for (size_t t = 0; t < c->timer.names.size(); ++t) if (!std::strcmp(c->timer.names[t], "chim_soft_fragments")) return c->timer.launches[t]; return (int64_t)0; };
+    c->timer.clear();
+    c->frags = F0;
+    c->nodes = N1;
+    bool fb = false;
+    int rc_d = dev_chimeric_edges(c, raw_d, fb);
+    if (!rc_d && fb) return fail(c, SQ_E_CAPACITY, "sq_debug_chim_stages: the device route handed stage 1 back to the host");
+    out8[3] = soft_seen();
+    if (!rc_d) {
+        reduce_edges(raw_d, red_d);
+        if ((rc_d = dev_chim_download_trimmed(c))) return rc_d;
+        if (!rc_h) out8[0] += same_blocks(h1, c->frags);
+        c->frags = F0;
+        c->nodes = N2; c->edges = E;
+        rc_d = dev_exact_breakpoints_start(c, fb);
+        if (!rc_d && fb) return fail(c, SQ_E_CAPACITY, "sq_debug_chim_stages: the device route handed stage 2 back to the host");
+        if (!rc_d) rc_d = dev_exact_breakpoints_collect(c, bp_d);
+        out8[4] = soft_seen() - out8[3];
+        if (!rc_d) { const int r3 = dev_chim_download_trimmed(c); if (r3) return r3; if (!rc_h) out8[0] += same_blocks(h2, c->frags); }
+    }
+    dev_flush_timers(c);
+    out8[6] = rc_d;
+    c->err.clear();
+    if (rc_h != rc_d) out8[0] += 1;
+    if (!rc_h && !rc_d) {
+        if (red_h.size() != red_d.size()) out8[0] += 1;
+        for (size_t i = 0; i < std::min(red_h.size(), red_d.size()); ++i) if (!edge_key_eq(red_h[i], red_d[i]) || red_h[i].w != red_d[i].w) out8[0] += 1;
+        for (const Edge& e : E) {  // (call_sv only ever looks up the keys of final edges)
+            const BPMap::const_iterator a = bp_h.find(edge_pack(e)), b = bp_d.find(edge_pack(e));
+            const bool ha = a != bp_h.end(), hb = b != bp_d.end();
+            if (ha != hb || (ha && a->second != b->second)) out8[0] += 1;
+        }
+    }
+    c->frags.clear(); c->frags0.clear(); c->nodes.clear(); c->edges.clear(); ++c->frags_version;
+    return SQ_OK;
+}
+int sq_debug_chim_stages(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
+                         const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8) {
+    return abi_guard(c, "sq_debug_chim_stages", [&]() { return sq_debug_chim_stages_impl(c, n1, nodes1, n2, nodes2, n_frag, frag_off, frag_na, frag_tot, blocks6, n_edges, edges4, out8); });
 }
 int sq_debug_order(sq_ctx* c, int32_t n, int32_t n_edges, const int32_t* edges5, int32_t use_gpu, int32_t* mask, int32_t* order, int64_t* value) {
     if (!c || n_edges < 0 || (n_edges && !edges5) || !mask || !order || !value) return SQ_E_ARG;

@@ -266,6 +266,7 @@ int build_fragments(sq_ctx* c, const sq_aln_batch* b) {
         for (int64_t k = lo; k < hi; ++k) { Frag& f = c->frags[(size_t)k]; f.a.release(); f.b.release(); std::string().swap(f.name); }
     });
     c->frags.clear();
+    ++c->frags_version;  // (the device's fragment table is made again)
     std::vector<Frag>& out = c->frags;
     std::vector<uint8_t> kept(nm, 0);     // by merged index
     std::vector<uint8_t> keep_at(nm, 0);  // by position in the sorted order

@@ -127,6 +127,15 @@ bool frag_first_block_pins(const std::vector<Node>& N, const Frag& f, int& node)
     node = ff.node;
     return ff.deep;
 }
+int chim_stage_soft_count(const sq_ctx* c, const std::vector<Node>& N, int stage) {
+    int n = 0;
+    for (const Frag& f : c->frags) {
+        if (stage == 1 ? (f.a.empty() && f.b.empty()) : (f.a.size() <= 1 && f.b.size() <= 1)) continue;
+        const FirstFit ff = first_block_fit(N, f);
+        if (!ff.deep && !ff.none) ++n;
+    }
+    return n;
+}
 namespace {
 // piece boundaries over the fragments `skip` does not drop, and the search start of every piece; false: run serially
 template <class Skip>

@@ -269,6 +269,13 @@ struct sq_ctx {
     std::vector<std::string> chim_names;        // sorted unique, incl. "" (ledger B9)
     std::unordered_set<std::string> chim_set;
     int64_t n_chim_records = 0;
+    // RawEdgesChim / ExactBreakpoint on the device (sq_chimeric_on_device; SQUID_CHIM_STAGES_GPU=1 / =0, read by sq_create, forces / forbids it)
+    uint64_t frags_version = 0;       // grows with every new set of fragments (the device's fragment table follows it)
+    bool chim_dev_asked = false;      // what the call said
+    int chim_dev_env = -1;            // the override: -1 none
+    bool chim_s1_device = false;      // this graph's RawEdgesChim ran on the device: c->frags is untrimmed, the trimmed blocks are in HBM
+    bool chim_s2_pending = false;     // ExactBreakpoint is queued on the stream (dev_exact_breakpoints_start); sq_call_sv collects it
+    bool chim_dev_on() const { return !bwa && (chim_dev_env >= 0 ? chim_dev_env != 0 : chim_dev_asked); }
     // concordant side (device)
     sq::DeviceRecords* dev = nullptr;
     // --bwa (sq_ingest_bwa_file): every record of the one BAM file on the host, with its QNAME (sq_bwa.cpp)
@@ -438,6 +445,7 @@ int further_compress(sq_ctx* c);
 void multiply_discordant(sq_ctx* c, bool undo);
 typedef std::map<uint64_t, std::vector<std::pair<int, int>>> BPMap;
 int exact_breakpoints(sq_ctx* c, BPMap& bp);
+int chim_stage_soft_count(const sq_ctx* c, const std::vector<Node>& N, int stage);  // soft fragments of a stage by first_block_fit (tools/chim_stage_emu.cpp, sq_debug_chim_stages)
 
 // ---- sq_order.cpp
 int order_components(sq_ctx* c);
@@ -482,6 +490,13 @@ int dev_filter_by_interleaving(sq_ctx* c, std::vector<uint8_t>& keep);
 int dev_filter_edges(sq_ctx* c, const std::vector<uint8_t>& keep);
 int dev_compress_nodes(sq_ctx* c);
 int dev_further_compress(sq_ctx* c);  // 2: capacity exceeded, take the host version
+// RawEdgesChim / ExactBreakpoint + CountTop on the device (sq_chim_stage.inc).  fallback: the stage has more soft fragments than the bound
+// (SQUID_CHIM_SOFT_MAX, default 2^20) and nothing was done -- the caller takes the host route
+int dev_chimeric_edges(sq_ctx* c, std::vector<Edge>& raw, bool& fallback);
+int dev_exact_breakpoints_start(sq_ctx* c, bool& fallback);  // queued behind the final graph; ..._collect waits for its event
+int dev_exact_breakpoints_collect(sq_ctx* c, BPMap& bp);
+void dev_chim_drop_pending(sq_ctx* c);
+int dev_chim_download_trimmed(sq_ctx* c);  // the blocks as the device trimmed them, into c->frags
 int dev_connected_components(sq_ctx* c, int n_nodes, const std::vector<Edge>& edges, std::vector<int32_t>& label);
 struct SmallProblem { int n; int eoff, ecount; };  // edges: local u,v,hu,hv,w packed as 5 ints each
 int dev_order_small(sq_ctx* c, const std::vector<SmallProblem>& probs, const std::vector<int32_t>& edges5, std::vector<int32_t>& out_mask,

@@ -34,6 +34,7 @@
 #include "sq_internal.h"
 #include "sq_inflate_spec.inc"
 #include "sq_resolve.inc"
+#include "sq_chim_stage.inc"
 
 #define HIPCHK(call)                                                                                         \
     do {                                                                                                     \
@@ -176,7 +177,36 @@ struct FeedPool {
     void wait() { std::unique_lock<std::mutex> lk(mu); done_cv.wait(lk, [&]() { return running == 0; }); }
 };
 
+// The chimeric graph stages on the device (sq_chim_stage.inc, dev_chimeric_edges / dev_exact_breakpoints_*): the fragment table -- made
+// once per set of fragments, read only --, the blocks as the stages trimmed them, the position chain, the hit groups of stage 2.  Its
+// own page-locked staging: stage 2 is in flight while other stages use DeviceRecords::pin.
+struct ChimStage {
+    uint64_t version = 0;  // sq_ctx::frags_version the table was made from (0: none)
+    int64_t nf = 0, nblk = 0;
+    DBuf<uint32_t> table;  // off | na | atot | btot | refid | refpos | readpos | matchref | matchread, then the bytes low | rev
+    DBuf<int32_t> trim, rn, pin, lastdeep, spos, sout, nodes, hit, goff, pairs, score, out;
+    DBuf<uint32_t> soft, hist, flags, hval, oval;
+    DBuf<unsigned long long> hkey, okey, ekey;
+    DBuf<uint8_t> cls;
+    uint32_t h_slots = 1u << 12;
+    Pinned stage;
+    hipEvent_t done = nullptr;
+    // stage 2 in flight (dev_exact_breakpoints_start .. _collect)
+    std::vector<unsigned long long> keys;  // of the final edges
+    const int32_t* h_out = nullptr;        // out_n (m) | out_xy (10 m), page-locked
+    chs::Frags F{};
+    chs::Trim T{};
+    void release() {
+        table.release(); trim.release(); rn.release(); pin.release(); lastdeep.release(); spos.release(); sout.release(); nodes.release(); hit.release(); goff.release();
+        pairs.release(); score.release(); out.release(); soft.release(); hist.release(); flags.release(); hval.release(); oval.release(); hkey.release(); okey.release();
+        ekey.release(); cls.release(); stage.release();
+        if (done) { (void)hipEventDestroy(done); done = nullptr; }
+        version = 0;
+    }
+};
+
 struct DeviceRecords {
+    ChimStage chim;
     int64_t n = 0, nb = 0;
     Pinned pin;
     DBuf<int32_t> refid, pos, mrefid, mpos, endpos, b_refpos, b_matchref;
@@ -3036,6 +3066,7 @@ int dev_create(sq_ctx* c) {
 void dev_destroy(sq_ctx* c) {
     if (!c->dev) return;
     DeviceRecords& D = *c->dev;
+    D.chim.release();
     D.refid.release(); D.pos.release(); D.mrefid.release(); D.mpos.release(); D.endpos.release(); D.b_refpos.release(); D.b_matchref.release();
     D.b_pack.release(); D.n_pack.release(); D.r_pack.release();
     D.flag.release(); D.totlen.release(); D.b_readpos.release(); D.b_matchread.release(); D.mapq.release(); D.aux.release(); D.blk_off.release();
@@ -4958,6 +4989,276 @@ int dev_breakpoint_support_exact(sq_ctx* c, const std::vector<std::pair<int, int
     }
     c->timer.add("host_bp_cursor_exact", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 0);
     return SQ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ chimeric graph stages on the device
+// (sq_chimeric_on_device; the kernels' bodies are in sq_chim_stage.inc)
+__global__ void k_chim_classify(chs::Nodes N, chs::Frags F, const int32_t* refpos, const int32_t* matchref, int stage, chs::Chain C) {
+    chs::classify(N, F, refpos, matchref, stage, C, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_chim_soft_list(chs::Frags F, chs::Chain C) { chs::soft_list(F, C, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ void k_chim_soft_resolve(chs::Nodes N, chs::Frags F, const int32_t* refpos, const int32_t* readpos, const int32_t* matchref, const int32_t* matchread, chs::Chain C, const uint32_t* nsoft) {
+    const uint32_t ns = *nsoft < C.soft_cap ? *nsoft : C.soft_cap;
+    chs::soft_resolve(N, F, refpos, readpos, matchref, matchread, C, ns, blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_chim_edges(chs::Nodes N, chs::Frags F, chs::Trim T, int32_t* rn, chs::Chain C, chs::Params P, unsigned long long* hk, uint32_t* hv, uint32_t mask, uint32_t* flags) {
+    chs::stage1_fragment(N, F, T, rn, C, P, hk, hv, mask, flags, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_chim_hits(chs::Nodes N, chs::Frags F, chs::Trim T, int32_t* rn, chs::Chain C, chs::Params P, const unsigned long long* ekey, int32_t m, int32_t* hit_e, int32_t* hit_b1,
+                            int32_t* hit_b2, uint32_t* hist) {
+    chs::stage2_fragment(N, F, T, rn, C, P, ekey, m, hit_e, hit_b1, hit_b2, hist, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ void k_chim_scatter(int64_t nblk, const int32_t* hit_e, const int32_t* hit_b1, const int32_t* hit_b2, const int32_t* goff, uint32_t* cursor, int32_t* p1, int32_t* p2) {
+    chs::scatter_hit(nblk, hit_e, hit_b1, hit_b2, goff, cursor, p1, p2, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_chim_count_top(int32_t m, const unsigned long long* ekey, const int32_t* goff, const int32_t* p1, const int32_t* p2, int32_t* score, int32_t* out_n, int32_t* out_xy) {
+    const int32_t e = (int32_t)(blockIdx.x * 4u + (threadIdx.x >> 6));  // one wave per final edge
+    if (e >= m) return;
+    chs::count_top_wave(e, goff, p1, p2, score, (ekey[e] >> 1) & 1, ekey[e] & 1, out_n, out_xy);
+}
+struct FChimDeep { const int32_t* pin; __device__ int operator()(int64_t i) const { return pin[i] >= 0 ? (int)i : -1; } };
+struct FChimSoft { const uint8_t* cls; __device__ int operator()(int64_t i) const { return cls[i] == chs::CLS_SOFT ? 1 : 0; } };
+struct FChimHist { const uint32_t* h; __device__ int operator()(int64_t i) const { return (int)h[i]; } };
+
+// more soft fragments than this in one stage: the stage goes back to the host (SQUID_CHIM_SOFT_MAX: a debug bound, the tests force the fallback with 0)
+static uint32_t chim_soft_max() {
+    const char* v = std::getenv("SQUID_CHIM_SOFT_MAX");
+    return v ? (uint32_t)std::max(0l, std::atol(v)) : (1u << 20);
+}
+
+// the fragment table: flattened on the host threads into one page-locked buffer, one copy.  From the untrimmed fragments (frags0).
+static int chim_upload_table(sq_ctx* c) {
+    ChimStage& S = c->dev->chim;
+    if (S.version == c->frags_version && S.version != 0) return SQ_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::vector<Frag>& src = c->frags0.size() == c->frags.size() ? c->frags0 : c->frags;
+    const size_t nf = src.size();
+    std::vector<uint32_t> off(nf + 1, 0);
+    for (size_t q = 0; q < nf; ++q) {
+        const size_t nxt = (size_t)off[q] + src[q].a.size() + src[q].b.size();
+        if (nxt > 0x7fffffffull) return fail(c, SQ_E_CAPACITY, "more than 2^31 chimeric blocks");
+        off[q + 1] = (uint32_t)nxt;
+    }
+    if (nf > 0x7ffffff0ull) return fail(c, SQ_E_CAPACITY, "more than 2^31 chimeric fragments");
+    const size_t nblk = off[nf], words = 4 * nf + 1 + 5 * nblk, bytes = words * 4 + nf + nblk;
+    uint8_t* h = nullptr;
+    HIPCHK(hipHostMalloc((void**)&h, std::max<size_t>(bytes, 64), hipHostMallocDefault));
+    uint32_t* w = (uint32_t*)h;
+    uint32_t *h_off = w, *h_na = h_off + nf + 1;
+    int32_t *h_atot = (int32_t*)(h_na + nf), *h_btot = h_atot + nf, *h_refid = h_btot + nf, *h_refpos = h_refid + nblk, *h_readpos = h_refpos + nblk, *h_matchref = h_readpos + nblk,
+            *h_matchread = h_matchref + nblk;
+    uint8_t *h_low = (uint8_t*)(h_matchread + nblk), *h_rev = h_low + nf;
+    std::memcpy(h_off, off.data(), (nf + 1) * 4);
+    const int pieces = (int)std::min<size_t>(nf, 256);
+    auto fill = [&](int pi) {
+        for (size_t q = nf * (size_t)pi / pieces; q < nf * ((size_t)pi + 1) / pieces; ++q) {
+            const Frag& f = src[q];
+            h_na[q] = (uint32_t)f.a.size(); h_atot[q] = f.atot; h_btot[q] = f.btot; h_low[q] = (uint8_t)((f.alow ? 1 : 0) | (f.blow ? 2 : 0));
+            size_t k = off[q];
+            for (int mate = 0; mate < 2; ++mate)
+                for (const Blk& b : (mate ? f.b : f.a)) {
+                    h_refid[k] = b.refid; h_refpos[k] = b.refpos; h_readpos[k] = b.readpos; h_matchref[k] = b.matchref; h_matchread[k] = b.matchread; h_rev[k] = b.rev ? 1 : 0;
+                    ++k;
+                }
+        }
+    };
+    if (pieces > 1 && c->pool) c->pool->parallel_for(pieces, 1 << 20, fill); else for (int pi = 0; pi < pieces; ++pi) fill(pi);
+    hipError_t e = S.table.reserve((bytes + 3) / 4 + 16);
+    if (e == hipSuccess) e = S.trim.reserve(4 * std::max<size_t>(nblk, 1));
+    if (e == hipSuccess) e = hipMemcpyAsync(S.table.p, h, bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipHostFree(h);
+    if (e != hipSuccess) return fail(c, SQ_E_HIP, std::string("chimeric fragment table: ") + hipGetErrorString(e));
+    S.nf = (int64_t)nf; S.nblk = (int64_t)nblk;
+    chs::Frags& F = S.F;
+    F.nf = S.nf; F.nblk = S.nblk;
+    F.off = S.table.p; F.na = F.off + nf + 1;
+    F.atot = (const int32_t*)(F.na + nf); F.btot = F.atot + nf; F.refid = F.btot + nf; F.refpos = F.refid + nblk; F.readpos = F.refpos + nblk; F.matchref = F.readpos + nblk;
+    F.matchread = F.matchref + nblk;
+    F.low = (const uint8_t*)(F.matchread + nblk); F.rev = F.low + nf;
+    S.T.refpos = S.trim.p; S.T.readpos = S.trim.p + nblk; S.T.matchref = S.trim.p + 2 * nblk; S.T.matchread = S.trim.p + 3 * nblk;
+    S.version = c->frags_version;
+    c->timer.add("chim_upload", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), (double)bytes);
+    return SQ_OK;
+}
+// node table of a stage (the final nodes have no position index: plain chr | pos | len, searched by bisection)
+static int chim_upload_nodes(sq_ctx* c, const std::vector<Node>& nodes, chs::Nodes& N) {
+    ChimStage& S = c->dev->chim;
+    const size_t n = nodes.size();
+    HIPCHK(S.nodes.reserve(3 * std::max<size_t>(n, 1)));
+    int32_t* h = S.stage.take_n<int32_t>(3 * n);
+    if (!h) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
+    for (size_t i = 0; i < n; ++i) { h[i] = nodes[i].chr; h[n + i] = nodes[i].pos; h[2 * n + i] = nodes[i].len; }
+    if (n) HIPCHK(hipMemcpyAsync(S.nodes.p, h, 3 * n * 4, hipMemcpyHostToDevice, c->stream));
+    N.n = (int32_t)n; N.chr = S.nodes.p; N.pos = S.nodes.p + n; N.len = S.nodes.p + 2 * n;
+    return SQ_OK;
+}
+// classification, the two scans, the soft list and its runs: the position chain of a stage.  flags[4] = number of soft fragments.
+static int chim_chain(sq_ctx* c, const chs::Nodes& N, int stage, chs::Chain& C) {
+    DeviceRecords& D = *c->dev;
+    ChimStage& S = D.chim;
+    hipStream_t s = c->stream;
+    const int64_t nf = S.nf;
+    const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)chim_soft_max(), nf);
+    HIPCHK(S.pin.reserve(nf)); HIPCHK(S.lastdeep.reserve(nf)); HIPCHK(S.spos.reserve(nf)); HIPCHK(S.cls.reserve(nf)); HIPCHK(S.soft.reserve(cap + 1)); HIPCHK(S.sout.reserve(cap + 1));
+    HIPCHK(S.flags.reserve(8));
+    C.pin = S.pin.p; C.lastdeep = S.lastdeep.p; C.spos = S.spos.p; C.soft = S.soft.p; C.sout = S.sout.p; C.cls = S.cls.p; C.soft_cap = cap;
+    const chs::Frags& F = S.F;
+    const int32_t *refpos = stage == 1 ? F.refpos : S.T.refpos, *readpos = stage == 1 ? F.readpos : S.T.readpos, *matchref = stage == 1 ? F.matchref : S.T.matchref,
+                  *matchread = stage == 1 ? F.matchread : S.T.matchread;
+    HIPCHK(hipMemsetAsync(S.flags.p, 0, 8 * 4, s));
+    { EvTimer t(c, "k_chim_classify", 13.0 * nf); hipLaunchKernelGGL(k_chim_classify, grid_for(nf, 256), dim3(256), 0, s, N, F, refpos, matchref, stage, C); }
+    { EvTimer t(c, "k_chim_scan", 17.0 * nf);
+      HIPCHK((device_scan<OpMax, true>(s, nf, FChimDeep{S.pin.p}, S.lastdeep.p, D.spine, nullptr)));
+      HIPCHK((device_scan<OpSum, true>(s, nf, FChimSoft{S.cls.p}, S.spos.p, D.spine, (int32_t*)(S.flags.p + 4)))); }
+    { EvTimer t(c, "k_chim_soft", 5.0 * nf);
+      hipLaunchKernelGGL(k_chim_soft_list, grid_for(nf, 256), dim3(256), 0, s, F, C);
+      if (cap) hipLaunchKernelGGL(k_chim_soft_resolve, grid_for(cap, 64), dim3(64), 0, s, N, F, refpos, readpos, matchref, matchread, C, (const uint32_t*)(S.flags.p + 4)); }
+    return SQ_OK;
+}
+
+// RawEdgesChim on the device: the (key, count) list joins `raw`.  fallback: the stage has more soft fragments than the bound -- nothing
+// was added, the caller takes the host route (same results).
+int dev_chimeric_edges(sq_ctx* c, std::vector<Edge>& raw, bool& fallback) {
+    DeviceRecords& D = *c->dev;
+    ChimStage& S = D.chim;
+    hipStream_t s = c->stream;
+    fallback = false;
+    if (c->nodes.empty()) { fallback = true; return SQ_OK; }
+    int rc = chim_upload_table(c);
+    if (rc) return rc;
+    const int64_t nf = S.nf;
+    if (nf == 0) return SQ_OK;
+    S.stage.reset();
+    chs::Nodes N;
+    if ((rc = chim_upload_nodes(c, c->nodes, N))) return rc;
+    chs::Chain C;
+    if ((rc = chim_chain(c, N, 1, C))) return rc;
+    HIPCHK(S.rn.reserve(std::max<int64_t>(S.nblk, 1)));
+    uint32_t* h = S.stage.take_n<uint32_t>(8);
+    if (!h) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
+    const chs::Params P{c->P.concord_dist_pos, c->P.concord_dist_idx};
+    while (S.h_slots < (1u << 28) && (size_t)S.h_slots < 4 * c->nodes.size()) S.h_slots <<= 1;
+    for (bool first = true;; first = false) {  // the table starts small and grows when it fills up (unique edges are few)
+        const uint32_t slots = S.h_slots;
+        HIPCHK(S.hkey.reserve(slots)); HIPCHK(S.hval.reserve(slots)); HIPCHK(S.okey.reserve(slots)); HIPCHK(S.oval.reserve(slots));
+        HIPCHK(hipMemsetAsync(S.hkey.p, 0xff, (size_t)slots * 8, s));
+        HIPCHK(hipMemsetAsync(S.hval.p, 0, (size_t)slots * 4, s));
+        if (!first) HIPCHK(hipMemsetAsync(S.flags.p, 0, 4 * 4, s));  // (flags[4], the soft count, stays)
+        { EvTimer t(c, "k_chim_edges", 9.0 * nf + 45.0 * S.nblk);
+          hipLaunchKernelGGL(k_chim_edges, grid_for(nf, 256), dim3(256), 0, s, N, S.F, S.T, S.rn.p, C, P, S.hkey.p, S.hval.p, slots - 1, S.flags.p); }
+        { EvTimer t(c, "k_chim_compact", 12.0 * slots); hipLaunchKernelGGL(k_hash_compact, grid_for(slots, 256), dim3(256), 0, s, S.hkey.p, S.hval.p, slots, (int32_t*)(S.flags.p + 1), S.okey.p, S.oval.p); }
+        HIPCHK(hipMemcpyAsync(h, S.flags.p, 8 * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (h[4] > chim_soft_max()) { fallback = true; return SQ_OK; }
+        if (!(h[0] & chs::FLAG_FULL)) break;
+        if (S.h_slots >= (1u << 28)) return fail(c, SQ_E_CAPACITY, "edge hash table full");
+        S.h_slots <<= 2;
+    }
+    c->timer.add("chim_soft_fragments", 0, 0, (int64_t)h[4]);
+    if (h[0] & chs::FLAG_ASSERT) return fail(c, SQ_E_ASSERT, "chimeric block outside the node table (reference: out-of-range edge, SegmentGraph.cpp:1410)");
+    const size_t cnt = h[1];
+    unsigned long long* hk = S.stage.take_n<unsigned long long>(cnt);
+    uint32_t* hv = S.stage.take_n<uint32_t>(cnt);
+    if (!hk || !hv) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
+    if (cnt) { HIPCHK(hipMemcpyAsync(hk, S.okey.p, cnt * 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(hv, S.oval.p, cnt * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
+    raw.reserve(raw.size() + cnt);
+    for (size_t i = 0; i < cnt; ++i) {
+        Edge e;
+        e.a = (int32_t)(hk[i] >> 32); e.b = (int32_t)((hk[i] & 0xffffffffull) >> 2); e.ha = (hk[i] >> 1) & 1; e.hb = hk[i] & 1; e.w = (int32_t)hv[i]; e.gw = 0;
+        raw.push_back(e);
+    }
+    return SQ_OK;
+}
+
+// the blocks as the device trimmed them, into c->frags (a stage that goes back to the host behind a device stage; sq_debug_chim_stages)
+int dev_chim_download_trimmed(sq_ctx* c) {
+    ChimStage& S = c->dev->chim;
+    const size_t nf = (size_t)S.nf, nblk = (size_t)S.nblk;
+    if (c->frags.size() != nf) return fail(c, SQ_E_ARG, "internal: the fragment table does not belong to these fragments");
+    std::vector<int32_t> t(4 * std::max<size_t>(nblk, 1));
+    if (nblk) { HIPCHK(hipMemcpyAsync(t.data(), S.trim.p, 4 * nblk * 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(hipStreamSynchronize(c->stream)); }
+    size_t k = 0;
+    for (Frag& f : c->frags)
+        for (int mate = 0; mate < 2; ++mate)
+            for (Blk& b : (mate ? f.b : f.a)) {
+                if (k >= nblk) return fail(c, SQ_E_ARG, "internal: the fragment table does not belong to these fragments");
+                b.refpos = t[k]; b.readpos = t[nblk + k]; b.matchref = t[2 * nblk + k]; b.matchread = t[3 * nblk + k];
+                ++k;
+            }
+    return SQ_OK;
+}
+
+// ExactBreakpoint + CountTop on the device, started behind the final graph: everything is queued on the stream, the results land in
+// page-locked memory and `done` says when.  fallback: as above (decided before anything is trimmed).
+int dev_exact_breakpoints_start(sq_ctx* c, bool& fallback) {
+    DeviceRecords& D = *c->dev;
+    ChimStage& S = D.chim;
+    hipStream_t s = c->stream;
+    fallback = false;
+    const std::vector<Edge>& E = c->edges;
+    const int32_t m = (int32_t)E.size();
+    S.keys.resize((size_t)m);
+    for (int32_t i = 0; i < m; ++i) S.keys[(size_t)i] = edge_pack(E[(size_t)i]);
+    if (c->nodes.empty() || S.version != c->frags_version || S.version == 0 || !std::is_sorted(S.keys.begin(), S.keys.end())) { fallback = true; return SQ_OK; }
+    const int64_t nf = S.nf, nblk = S.nblk;
+    S.stage.reset();
+    int32_t* h_out = S.stage.take_n<int32_t>(11 * (size_t)m);
+    uint32_t* h = S.stage.take_n<uint32_t>(8);
+    unsigned long long* h_keys = S.stage.take_n<unsigned long long>((size_t)m);
+    if (!h_out || !h || !h_keys) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
+    S.h_out = h_out;
+    if (!S.done) HIPCHK(hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    if (nf == 0 || m == 0) { std::memset(h_out, 0, 11 * (size_t)m * 4); HIPCHK(hipEventRecord(S.done, s)); return SQ_OK; }
+    chs::Nodes N;
+    int rc = chim_upload_nodes(c, c->nodes, N);
+    if (rc) return rc;
+    chs::Chain C;
+    if ((rc = chim_chain(c, N, 2, C))) return rc;
+    HIPCHK(hipMemcpyAsync(h, S.flags.p, 8 * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));  // (the soft count decides the route before the blocks are trimmed any further)
+    if (h[4] > chim_soft_max()) { fallback = true; return SQ_OK; }
+    c->timer.add("chim_soft_fragments", 0, 0, (int64_t)h[4]);
+    std::memcpy(h_keys, S.keys.data(), (size_t)m * 8);
+    HIPCHK(S.ekey.reserve((size_t)m)); HIPCHK(S.hit.reserve(3 * std::max<int64_t>(nblk, 1))); HIPCHK(S.hist.reserve(2 * (size_t)m)); HIPCHK(S.goff.reserve((size_t)m + 1));
+    HIPCHK(S.pairs.reserve(2 * std::max<int64_t>(nblk, 1))); HIPCHK(S.score.reserve(std::max<int64_t>(nblk, 1))); HIPCHK(S.out.reserve(11 * (size_t)m)); HIPCHK(S.rn.reserve(std::max<int64_t>(nblk, 1)));
+    HIPCHK(hipMemcpyAsync(S.ekey.p, h_keys, (size_t)m * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(S.hit.p, 0xff, (size_t)std::max<int64_t>(nblk, 1) * 4, s));
+    HIPCHK(hipMemsetAsync(S.hist.p, 0, 2 * (size_t)m * 4, s));
+    int32_t *hit_e = S.hit.p, *hit_b1 = S.hit.p + nblk, *hit_b2 = S.hit.p + 2 * nblk, *p1 = S.pairs.p, *p2 = S.pairs.p + nblk, *out_n = S.out.p, *out_xy = S.out.p + m;
+    uint32_t *hist = S.hist.p, *cursor = S.hist.p + m;
+    const chs::Params P{c->P.concord_dist_pos, c->P.concord_dist_idx};
+    { EvTimer t(c, "k_chim_hits", 9.0 * nf + 45.0 * nblk);
+      hipLaunchKernelGGL(k_chim_hits, grid_for(nf, 256), dim3(256), 0, s, N, S.F, S.T, S.rn.p, C, P, S.ekey.p, m, hit_e, hit_b1, hit_b2, hist); }
+    { EvTimer t(c, "k_chim_scan", 8.0 * m);
+      HIPCHK((device_scan<OpSum, true>(s, m, FChimHist{hist}, S.goff.p, D.spine, S.goff.p + m))); }
+    { EvTimer t(c, "k_chim_scatter", 4.0 * nblk); hipLaunchKernelGGL(k_chim_scatter, grid_for(std::max<int64_t>(nblk, 1), 256), dim3(256), 0, s, nblk, hit_e, hit_b1, hit_b2, S.goff.p, cursor, p1, p2); }
+    { EvTimer t(c, "k_chim_count_top", 0); hipLaunchKernelGGL(k_chim_count_top, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, m, S.ekey.p, S.goff.p, p1, p2, S.score.p, out_n, out_xy); }
+    HIPCHK(hipMemcpyAsync(h_out, S.out.p, 11 * (size_t)m * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipEventRecord(S.done, s));
+    return SQ_OK;
+}
+int dev_exact_breakpoints_collect(sq_ctx* c, BPMap& bp) {
+    ChimStage& S = c->dev->chim;
+    bp.clear();
+    if (!S.done || !S.h_out) return fail(c, SQ_E_ARG, "internal: no breakpoint stage in flight");
+    HIPCHK(hipEventSynchronize(S.done));
+    const size_t m = S.keys.size();
+    const int32_t *out_n = S.h_out, *out_xy = S.h_out + m;
+    for (size_t e = 0; e < m; ++e) {
+        if (out_n[e] <= 0) continue;
+        std::vector<std::pair<int, int>> x;
+        for (int k = 0; k < out_n[e] && k < 5; ++k) x.push_back(std::make_pair(out_xy[10 * e + 2 * (size_t)k], out_xy[10 * e + 2 * (size_t)k + 1]));
+        bp.emplace_hint(bp.end(), S.keys[e], std::move(x));
+    }
+    S.h_out = nullptr;
+    return SQ_OK;
+}
+void dev_chim_drop_pending(sq_ctx* c) {
+    if (!c->dev) return;
+    ChimStage& S = c->dev->chim;
+    if (S.done && S.h_out) (void)hipEventSynchronize(S.done);
+    S.h_out = nullptr;
 }
 
 #include "sq_graph_kernels.inc"

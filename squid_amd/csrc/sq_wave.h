@@ -78,6 +78,10 @@ WV_FN u32x4 load16(const uint32_t* p) { return u32x4{p[0], p[1], p[2], p[3]}; }
 WV_FN void lds_st32(lds_u8* p, uint32_t v) { std::memcpy(p, &v, 4); }
 WV_FN void lds_st64(lds_u8* p, unsigned long long v) { std::memcpy(p, &v, 8); }
 WV_FN uint32_t lds_ld32(const lds_u8* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
+// (global-memory atomics of sq_chim_stage.inc: one host thread, so plain reads and writes)
+WV_FN uint32_t glb_atomic_add(uint32_t* p, uint32_t v) { const uint32_t o = *p; *p = o + v; return o; }
+WV_FN uint32_t glb_atomic_or(uint32_t* p, uint32_t v) { const uint32_t o = *p; *p = o | v; return o; }
+WV_FN unsigned long long glb_atomic_cas64(unsigned long long* p, unsigned long long expect, unsigned long long v) { const unsigned long long o = *p; if (o == expect) *p = v; return o; }
 // run fn(arg) as a wave of 64 lanes; returns when every lane has returned
 inline void run_wave(void (*fn)(void*), void* arg, size_t stack_bytes = 256 << 10) {
     Emu e;
@@ -149,5 +153,8 @@ WV_FN u32x4 load16(const uint32_t* p) { return *(const uint4*)p; }
 WV_FN void lds_st32(lds_u8* p, uint32_t v) { typedef uint32_t __attribute__((aligned(1))) u; *(__attribute__((address_space(3))) u*)p = v; }
 WV_FN void lds_st64(lds_u8* p, unsigned long long v) { typedef unsigned long long __attribute__((aligned(1))) u; *(__attribute__((address_space(3))) u*)p = v; }
 WV_FN uint32_t lds_ld32(const lds_u8* p) { typedef uint32_t __attribute__((aligned(1))) u; return *(const __attribute__((address_space(3))) u*)p; }
+WV_FN uint32_t glb_atomic_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+WV_FN uint32_t glb_atomic_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
+WV_FN unsigned long long glb_atomic_cas64(unsigned long long* p, unsigned long long expect, unsigned long long v) { return atomicCAS(p, expect, v); }
 }  // namespace wv
 #endif
