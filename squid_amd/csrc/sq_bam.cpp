@@ -455,7 +455,7 @@ static int parse_bam_impl(const char* path, const ParseOpts& o, size_t batch_rec
     using clk = std::chrono::steady_clock;
     double t_read = 0, t_inflate = 0, t_walk = 0, t_decode = 0, t_append = 0, t_sink = 0;
     auto since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
-    struct Report { double &a, &b, &c, &d, &e, &f; const char* path; ~Report() { if (std::getenv("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: read %.1f inflate %.1f walk %.1f decode %.1f append %.1f sink %.1f ms\n", path, a, b, c, d, e, f); } } report{t_read, t_inflate, t_walk, t_decode, t_append, t_sink, path};
+    struct Report { double &a, &b, &c, &d, &e, &f; const char* path; ~Report() { if (env_set("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: read %.1f inflate %.1f walk %.1f decode %.1f append %.1f sink %.1f ms\n", path, a, b, c, d, e, f); } } report{t_read, t_inflate, t_walk, t_decode, t_append, t_sink, path};
     auto tr0 = clk::now();
     FileBytes fb;
     if (!fb.load(path)) { err = std::string("cannot open bamfile ") + path; return SQ_E_IO; }
@@ -596,7 +596,7 @@ static int parse_bam_impl(const char* path, const ParseOpts& o, size_t batch_rec
             for (int t = 1; t < T; ++t) {
                 size_t hi = consumed + avail * (t + 1) / T;
                 if (s_begin[t] >= hi && parts[t].size() == 0 && roffs[t].empty() && good_end >= hi) { ++good; continue; }  // slice swallowed by a long record
-                if (s_begin[t] != good_end) { if (std::getenv("SQUID_INGEST_DEBUG")) std::fprintf(stderr, "stitch mismatch at slice %d/%d: begin=%zu expected=%zu lo=%zu hi=%zu\n", t, T, s_begin[t], good_end, consumed + avail * t / T, hi); break; }
+                if (s_begin[t] != good_end) { if (env_set("SQUID_INGEST_DEBUG")) std::fprintf(stderr, "stitch mismatch at slice %d/%d: begin=%zu expected=%zu lo=%zu hi=%zu\n", t, T, s_begin[t], good_end, consumed + avail * t / T, hi); break; }
                 if (prc[t]) { err = perr[t]; return prc[t]; }
                 good_end = s_end[t];
                 ++good;
@@ -890,7 +890,7 @@ struct FastInflate {
     typedef void (*free_fn)(void*);
     alloc_fn alloc = nullptr; run_fn run = nullptr; free_fn release = nullptr;
     FastInflate() {
-        if (std::getenv("SQUID_ZLIB_ONLY")) return;
+        if (env_set("SQUID_ZLIB_ONLY")) return;
         void* h = dlopen("libdeflate.so.0", RTLD_NOW | RTLD_LOCAL);
         if (!h) return;
         alloc = (alloc_fn)dlsym(h, "libdeflate_alloc_decompressor");
@@ -1071,17 +1071,16 @@ int scan_bam_file(const char* path, int n_threads, std::string& err, const RawSi
     // MI355X against ~0.5 GB/s per host thread, after a fixed start-up -- taken for files of at least 1 GiB when at
     // most 24 threads can really run (the caller's count, the affinity mask, the cgroup quota).  SQUID_GPU_INFLATE=1 / =0 forces / forbids it.  For a whole file the block index
     // is then built batch by batch while the GPU works (`lazy`: no page-table fill and no index walk up front).
-    const char* gpu_env = std::getenv("SQUID_GPU_INFLATE");
     struct stat fst;
     const size_t file_bytes = ::stat(path, &fst) == 0 ? (size_t)fst.st_size : 0;
     // (round 3 left files to the host pipeline when more than 24 host threads could run; with the streamed read the GPU reader is ahead
     // of any number of them)
     const bool gpu_auto = file_bytes >= ((size_t)1 << 30);
-    bool try_gpu = gpu && (force_gpu || (gpu_env ? std::atoi(gpu_env) != 0 : gpu_auto));
+    bool try_gpu = gpu && (force_gpu || (env_set("SQUID_GPU_INFLATE") ? env_nonzero("SQUID_GPU_INFLATE") : gpu_auto));
     // A chromosome shard with a .bai next to the BAM starts at the virtual offset of its first record and walks only the BGZF
     // blocks of its own range (lazily, like a whole file); without one, the whole file is indexed and the range is found by probing.
     BaiIndex bai;
-    static const bool no_bai_env = std::getenv("SQUID_NO_BAI") != nullptr;
+    static const bool no_bai_env = env_set("SQUID_NO_BAI");
     bool use_bai = only && try_gpu && allow_bai && !no_bai_env && bai.load(path, -1);
     const bool lazy = try_gpu && (!only || use_bai);
     bool map_reused = false;
@@ -1118,7 +1117,7 @@ int scan_bam_file(const char* path, int n_threads, std::string& err, const RawSi
     const size_t prefault_ahead = (size_t)1400 << 20;
     prefault.upto = prefault_ahead;
     // (a reused mapping has its page tables filled; a GPU reader that streams the file itself never looks at the mapping beyond the header)
-    const bool streams = lazy && gpu_streams && std::getenv("SQUID_NO_STREAM") == nullptr;
+    const bool streams = lazy && gpu_streams && !env_set("SQUID_NO_STREAM");
     if (lazy && !map_reused && !streams) prefault.start(fm.p, fm.n);
     std::vector<BgzfBlock> blocks;
     size_t total = 0;
@@ -1249,13 +1248,13 @@ int scan_bam_file(const char* path, int n_threads, std::string& err, const RawSi
         };
         const double t_before_gpu = since(t_all);
         GpuFileSrc src{path, ix.p, ix.total, ix.stop, false, false};
-        const int r2 = gpu(fm.p, br, nb, lazy ? (size_t)-1 : nb_end, only_begin, !unsynced, nref, lazy ? more : IndexMore(), gpu_file_bytes, gpu_streams && !std::getenv("SQUID_NO_STREAM") ? &src : nullptr);
+        const int r2 = gpu(fm.p, br, nb, lazy ? (size_t)-1 : nb_end, only_begin, !unsynced, nref, lazy ? more : IndexMore(), gpu_file_bytes, gpu_streams && !env_set("SQUID_NO_STREAM") ? &src : nullptr);
         if (r2 == SQ_OK && src.streamed && lazy && !index_cached) {  // the device side has walked the headers: its index is the index
             ix.p = src.walk_p; ix.total = src.walk_total; ix.bad = src.bad;
             blocks.resize(br.size());
             for (size_t i = 0; i < br.size(); ++i) { blocks[i].coff = br[i].coff; blocks[i].clen = br[i].clen; blocks[i].isize = br[i].isize; blocks[i].uoff = br[i].uoff; }
         }
-        if (std::getenv("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: map+index %.1f, header %.1f, GPU inflate+parse path total %.1f ms (rc %d)\n", path, t_map, t_before_gpu, since(t_all), r2);
+        if (env_set("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: map+index %.1f, header %.1f, GPU inflate+parse path total %.1f ms (rc %d)\n", path, t_map, t_before_gpu, since(t_all), r2);
         if (r2 != 2) {
             if (r2 == SQ_OK && lazy && !ix.complete()) { err = "not a BGZF file"; return SQ_E_IO; }
             if (r2 == SQ_OK && lazy && !only && !index_cached && ix.p == fm.n) g_map_cache.set_index(fm_hold, blocks, ix.total);
@@ -1264,7 +1263,7 @@ int scan_bam_file(const char* path, int n_threads, std::string& err, const RawSi
             prefault.finish();
             auto* junk = new std::pair<std::vector<BgzfBlock>, std::vector<BgzfRange>>(std::move(blocks), std::move(br));
             std::thread([junk]() { delete junk; }).detach();
-            if (std::getenv("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: returning after %.1f ms\n", path, since(t_all));
+            if (env_set("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: returning after %.1f ms\n", path, since(t_all));
             return r2;
         }
         if (lazy && use_bai) { prefault.finish(); return scan_bam_file(path, n_threads, err, sink, on_total, only, gpu, force_gpu, false, gpu_streams); }  // (start over on the probing path)
@@ -1337,7 +1336,7 @@ int scan_bam_file(const char* path, int n_threads, std::string& err, const RawSi
         cur ^= 1;
     }
     if (inflight.valid()) { auto tw0 = clk::now(); int r2 = inflight.get(); t_wait += since(tw0); if (!rc) rc = r2; }
-    if (std::getenv("SQUID_INGEST_TIMING"))
+    if (env_set("SQUID_INGEST_TIMING"))
         std::fprintf(stderr, "ingest %s: map+index %.1f inflate %.1f boundaries %.1f waiting for the GPU sink %.1f total %.1f ms (%d threads)\n", path, t_map, t_inflate, t_find, t_wait, since(t_all), n_threads);
     {   // giving 130 MB of touched pages back to the system takes ~20 ms: do it off the caller's path
         uint8_t *p0 = buf[0].p, *p1 = buf[1].p;

@@ -243,12 +243,15 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
     }
 }
 }  // namespace
+// SQUID_BWA_PIECE=<records>: length of a stretch of the parallel --bwa loops (tests: short stretches and a short warm-up on small inputs); 0: by size
+static long bwa_piece_env() { return (long)env_int("SQUID_BWA_PIECE", 0); }
+
 static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& seeds, std::vector<std::vector<Blk>>& reads) {
     const size_t nrec = hb.size();
     // ReadLen as the loop leaves it (:857-864): the chimeric file's value, raised by the first five records
     int RL_final = c->read_len;
     for (size_t ri = 0; ri < nrec && ri < 5; ++ri) RL_final = std::max(RL_final, (int)hb.totlen[ri]);
-    const long piece_env = std::getenv("SQUID_BWA_PIECE") ? std::atol(std::getenv("SQUID_BWA_PIECE")) : 0;
+    const long piece_env = bwa_piece_env();
     const int threads = c->pool ? c->pool->size() + 1 : 1;
     std::vector<size_t> cut{0};
     if (threads > 1 && nrec > 16 && (piece_env > 0 || nrec >= 200000)) {
@@ -338,12 +341,12 @@ static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& see
             if (!S.oth_set) S.other_right = real.other_right;
             continue;
         }
-        if (std::getenv("SQUID_BWA_DEBUG")) std::fprintf(stderr, "stretch %d (%d, %d) again: zero %d, rightmost values %d / %d against first true tests at %d / %d\n", k, hb.refid[cut[(size_t)k]], hb.pos[cut[(size_t)k]], real.zero, real.dis_right, real.other_right, S.minpos_dis, S.minpos_oth);
+        if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "stretch %d (%d, %d) again: zero %d, rightmost values %d / %d against first true tests at %d / %d\n", k, hb.refid[cut[(size_t)k]], hb.pos[cut[(size_t)k]], real.zero, real.dis_right, real.other_right, S.minpos_dis, S.minpos_oth);
         work(k, &real);
         ++again;
     }
     c->timer.add("bwa_seed_node_stretches_run_again", 0.0, 0.0, again);
-    if (std::getenv("SQUID_BWA_DEBUG")) {
+    if (env_set("SQUID_BWA_DEBUG")) {
         for (int k = 0; k < np; ++k) {
             std::fprintf(stderr, "stretch %d: records [%zu, %zu) first (%d, %d); seeds:", k, cut[(size_t)k], cut[(size_t)k + 1], hb.refid[cut[(size_t)k]], hb.pos[cut[(size_t)k]]);
             for (const Node& n : runs[(size_t)k].seeds) std::fprintf(stderr, " (%d %d %d)", n.chr, n.pos, n.len);
@@ -484,10 +487,10 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
         }
     };
     const auto t_re0 = std::chrono::steady_clock::now();
-    auto re_lap = [&](const char* what) { if (std::getenv("SQUID_BWA_DEBUG")) std::fprintf(stderr, "RawEdges: %-28s at %8.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_re0).count()); };
+    auto re_lap = [&](const char* what) { if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "RawEdges: %-28s at %8.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_re0).count()); };
     // stretch boundaries: behind the nearest record in front of an even cut that pins the position (looked for among the 4096 records
     // in front of the cut; none there: that cut is left out).  SQUID_BWA_PIECE=<records> sets the stretch length (tests: small inputs)
-    const long piece_env = std::getenv("SQUID_BWA_PIECE") ? std::atol(std::getenv("SQUID_BWA_PIECE")) : 0;
+    const long piece_env = bwa_piece_env();
     const size_t nrec = hb.size();
     const int threads = c->pool ? c->pool->size() + 1 : 1;
     std::vector<size_t> cut{0};
@@ -692,7 +695,7 @@ int bwa_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bp
         }
         return cur;
     };
-    const long piece_env = std::getenv("SQUID_BWA_PIECE") ? std::atol(std::getenv("SQUID_BWA_PIECE")) : 0;  // (tests: short stretches and a short warm-up on small inputs)
+    const long piece_env = bwa_piece_env();  // (tests: short stretches and a short warm-up on small inputs)
     const int np = !c->pool ? 1 : piece_env > 0 ? (int)std::min<size_t>(4096, std::max<size_t>(1, nrec / (size_t)piece_env)) : (nrec > 400000 ? 4 * (c->pool->size() + 1) : 1);
     const size_t warm_len = piece_env > 0 ? (size_t)piece_env : 65536;
     if (np == 1) { walk(0, nrec, 0, &cov); return SQ_OK; }

@@ -142,6 +142,9 @@ static void pack_seeds(sq_ctx* c, const GraphBuild& g) {
 }
 
 // CompressNode .. MultiplyDisEdges of the constructor (SegmentGraph.cpp:117-122), shared by the STAR and the --bwa path
+// SQUID_HOST_FILTERS: the edge filters and the node compression on the host (cross-check of the device route)
+static bool host_filters_env() { static const bool v = env_set("SQUID_HOST_FILTERS"); return v; }
+
 static int finish_graph(sq_ctx* c, bool host_filters) {
     int rc;
     {
@@ -197,7 +200,7 @@ static int build_graph_bwa(sq_ctx* c) {
     { HostClock hc(c, "host_edge_reduce"); reduce_edges(raw, c->edges, c->pool ? std::min(c->pool->size() + 1, 32) : 1); }
     c->counts.n_unique_edges = (int64_t)c->edges.size();
     if (c->keep_stages) c->snap[2].take(c->nodes, c->edges, nullptr);
-    static const bool host_filters = std::getenv("SQUID_HOST_FILTERS") != nullptr;
+    const bool host_filters = host_filters_env();
     {
         HostClock hc(c, host_filters ? "host_filters" : "wall_filters");
         std::vector<uint8_t> keep;
@@ -488,7 +491,7 @@ static int build_graph(sq_ctx* c) {
     // change inside the bounds; only then (or when SQUID_EXACT_DEPTH is set, as the stage-parity tests do) is the
     // reference's sort repeated on the host and the sweep walked exactly.  A sharded run cannot repeat that sort (its
     // tie order depends on the whole list) and fails loudly instead.
-    const bool exact_mode = std::getenv("SQUID_EXACT_DEPTH") != nullptr && !sh.on;
+    const bool exact_mode = env_set("SQUID_EXACT_DEPTH") && !sh.on;
     struct OtherR { int32_t chr, pos, len; };
     std::vector<OtherR> other_sorted;
     auto sort_other = [&]() { std::sort(other_sorted.begin(), other_sorted.end(), [](const OtherR& a, const OtherR& b) { return a.chr != b.chr ? a.chr < b.chr : a.pos < b.pos; }); };
@@ -542,7 +545,7 @@ static int build_graph(sq_ctx* c) {
         if (!other_sorted.empty()) exact_sweep(ocnt, osum);
         set_depths(ocnt, osum, false);
     } else set_depths(ocnt, osum, g.tiny_boundary);
-    static const bool host_filters = std::getenv("SQUID_HOST_FILTERS") != nullptr;
+    const bool host_filters = host_filters_env();
     if (!resumed) {
         if (c->keep_stages) c->snap[1].take(c->nodes, c->edges, nullptr);
         {
@@ -562,7 +565,7 @@ static int build_graph(sq_ctx* c) {
             if (host_filters) filter_by_interleaving(c, g.keep); else if ((rc = dev_filter_by_interleaving(c, g.keep))) return rc;
             g.before = c->edges;
             if (host_filters) filter_edges(c, g.keep); else if ((rc = dev_filter_edges(c, g.keep))) return rc;
-            if (std::getenv("SQUID_FORCE_DEPTH_RETRY")) c->depth_ambiguous = true;  // (tests: take the exact sweep whatever the bounds say)
+            if (env_set("SQUID_FORCE_DEPTH_RETRY")) c->depth_ambiguous = true;  // (tests: take the exact sweep whatever the bounds say)
         }
         if (c->depth_ambiguous || resumed) {
             // some coverage-ratio decision depends on the tie order: repeat the reference's sort and sweep, then redo the
@@ -690,7 +693,7 @@ static int call_sv(sq_ctx* c) {
         par(v.ebp.size(), [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; ++k) { BPs[2 * k] = v.ebp[k].first; BPs[2 * k + 1] = v.ebp[k].second; } });
         // (equal elements are indistinguishable pairs: any sort gives the reference's sorted list; the threaded introsort of sq_parsort.h)
         std_sort_parallel(BPs.begin(), BPs.end(), std::less<std::pair<int, int>>(), c->pool ? std::min(c->pool->size() + 1, 32) : 1, true);
-        static const bool bp_host = getenv("SQUID_BP_HOST") != nullptr;  // debug cross-check of k_bp_walk
+        static const bool bp_host = env_set("SQUID_BP_HOST");  // debug cross-check of k_bp_walk
         if (c->bwa) {  // (--bwa: the records and their names are on the host)
             rc = bwa_breakpoint_support(c, BPs, cov);
             if (rc) return rc;
@@ -845,7 +848,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     sq_ctx* c = new sq_ctx();
     c->P = *p;
     c->pool.reset(new HostPool(host_workers(p->world_size)));
-    if (const char* env = std::getenv("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = std::atoi(env) ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
+    if (env_set("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = env_nonzero("SQUID_CHIM_STAGES_GPU") ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
     *out = c;
@@ -975,7 +978,7 @@ int sq_read_header(const char* path, int32_t* n_ref, int32_t* ref_len, char* nam
 // the record parse of the concordant BAM waits for is kept -- the pairing goes on meanwhile
 static int chimeric_file_to_fragments(sq_ctx* c, const char* path, int nt, std::string& err, bool early = false, const HostBatch* decoded = nullptr) {
     const auto t_chim0 = std::chrono::steady_clock::now();
-    static const bool chim_prof = std::getenv("SQUID_CHIM_PROF") != nullptr;
+    static const bool chim_prof = env_set("SQUID_CHIM_PROF");
     auto lap = [&](const char* what) { if (chim_prof) std::fprintf(stderr, "chimeric file: %-28s at %8.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_chim0).count()); };
     drop_early_clusters(c);
     ParseOpts o{c->P.phred_type, c->P.min_phred, c->P.max_lowphred_len, true, nullptr};
@@ -1057,7 +1060,7 @@ static int chimeric_records_through_the_device(sq_ctx* c, const char* path, int 
                            [&](size_t total) { c->ingest_total_bytes = total; }, nullptr,
                            [&](const uint8_t* file, std::vector<BgzfRange>& blocks, size_t b0, size_t b1, size_t begin, bool synced, int nref, const IndexMore& more, size_t file_bytes, GpuFileSrc* src) {
                                return dev_ingest_bgzf(c, file, blocks, b0, b1, begin, synced, nref, more, file_bytes, src); }, false, true, true);
-    static const bool prof = std::getenv("SQUID_CHIM_PROF") != nullptr;
+    static const bool prof = env_set("SQUID_CHIM_PROF");
     const auto t0 = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) { if (prof) std::fprintf(stderr, "chimeric file on the device: %-24s at %8.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count()); };
     lap("reader returned (since then)");
@@ -1076,7 +1079,7 @@ static int chimeric_records_through_the_device(sq_ctx* c, const char* path, int 
 static int sq_ingest_files_impl(sq_ctx* c, const char* chim_path, const char* bam_path, int32_t n_threads) {
     if (!c || !chim_path || !bam_path) return SQ_E_ARG;
     if (c->bwa) return fail(c, SQ_E_ARG, "this context holds a --bwa batch (sq_ingest_bwa_file): sq_clear_records before a STAR-mode ingest -- the mode is per context");
-    if (std::getenv("SQUID_HOST_PARSE") || std::getenv("SQUID_SERIAL_LOAD")) {  // (the host parser consults the name set record by record)
+    if (env_set("SQUID_HOST_PARSE") || env_set("SQUID_SERIAL_LOAD")) {  // (the host parser consults the name set record by record)
         const int rc = sq_ingest_chimeric_file(c, chim_path);
         return rc ? rc : sq_ingest_concordant_file(c, bam_path, n_threads);
     }
@@ -1089,8 +1092,7 @@ static int sq_ingest_files_impl(sq_ctx* c, const char* chim_path, const char* ba
     std::shared_ptr<HostBatch> decoded;
     {
         struct stat st;
-        const char* env = std::getenv("SQUID_CHIM_GPU");
-        const bool want = env ? std::atoi(env) != 0 : (::stat(chim_path, &st) == 0 && (size_t)st.st_size >= ((size_t)128 << 20));
+        const bool want = env_set("SQUID_CHIM_GPU") ? env_nonzero("SQUID_CHIM_GPU") : (::stat(chim_path, &st) == 0 && (size_t)st.st_size >= ((size_t)128 << 20));
         if (want) {
             // (the batch is the context's between calls, like the scratch of a whole-file read on the host: 0.5 GB of pages on the dense
             // config that the next read of a chimeric file finds in place; sq_release_reader_buffers gives them back)
@@ -1124,7 +1126,7 @@ static int sq_ingest_concordant_file_impl(sq_ctx* c, const char* path, int32_t n
     if (!c || !path) return SQ_E_ARG;
     if (c->bwa) return fail(c, SQ_E_ARG, "this context holds a --bwa batch (sq_ingest_bwa_file): sq_clear_records before a STAR-mode ingest -- the mode is per context");
     { int r0 = sq_set_source(c, path); if (r0) return r0; }
-    if (!std::getenv("SQUID_HOST_PARSE")) {
+    if (!env_set("SQUID_HOST_PARSE")) {
         // default: the host only inflates BGZF and finds record boundaries; K0 parses the records on the GPU
         const auto t_file0 = std::chrono::steady_clock::now();
         c->ingest_total_bytes = 0; c->ingest_seen_bytes = 0;
@@ -1145,7 +1147,7 @@ static int sq_ingest_concordant_file_impl(sq_ctx* c, const char* path, int32_t n
         c->ingest_total_bytes = 0;
         const double t_scan = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_file0).count();
         dev_flush_timers(c);
-        if (std::getenv("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: reader returned after %.1f ms, timers flushed after %.1f ms\n", path, t_scan, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_file0).count());
+        if (env_set("SQUID_INGEST_TIMING")) std::fprintf(stderr, "ingest %s: reader returned after %.1f ms, timers flushed after %.1f ms\n", path, t_scan, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_file0).count());
         return rc;
     }
     if (c->chim_set.size() != c->chim_names.size()) { c->chim_set.clear(); c->chim_set.insert(c->chim_names.begin(), c->chim_names.end()); }
@@ -1171,8 +1173,7 @@ static int sq_ingest_bwa_file_impl(sq_ctx* c, const char* path, int32_t n_thread
         // record parse on the device, the QNAMEs kept next to the records (sq_ctx::capture_names, as for a large chimeric BAM), one copy
         // back -- the batch the host decoder below makes, field for field; the two order-dependent loops of the mode then run on it
         struct stat st;
-        const char* env = std::getenv("SQUID_BWA_GPU");
-        const bool want = env ? std::atoi(env) != 0 : (::stat(path, &st) == 0 && (size_t)st.st_size >= ((size_t)1 << 30));
+        const bool want = env_set("SQUID_BWA_GPU") ? env_nonzero("SQUID_BWA_GPU") : (::stat(path, &st) == 0 && (size_t)st.st_size >= ((size_t)1 << 30));
         if (want && chimeric_records_through_the_device(c, path, n_threads, *all, false) == SQ_OK) {
             c->bwa = all;
             c->counts.n_concordant = (int64_t)all->size();

@@ -87,7 +87,7 @@ int build_fragments(sq_ctx* c, const sq_aln_batch* b) {
         if (pieces <= 1 || !pool) { f(0, n); return; }
         pool->parallel_for(pieces, 15, [&](int k) { f(n * k / pieces, n * (k + 1) / pieces); });  // (allocation-heavy loops: measured on 9.6 M records, 'merge runs' 277 ms with 16 threads, 410 ms with 64 -- glibc's arenas)
     };
-    static const bool prof = std::getenv("SQUID_CHIM_PROF") != nullptr;
+    static const bool prof = env_set("SQUID_CHIM_PROF");
     auto t_prev = std::chrono::steady_clock::now();
     auto lap = [&](const char* what) {
         if (!prof) return;

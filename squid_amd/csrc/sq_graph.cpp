@@ -488,7 +488,7 @@ void filter_edges(sq_ctx* c, const std::vector<uint8_t>& keep) {
                     double inf = overlap ? 1.0 : std::min(ratio_of(na.depth_lo, nb.depth_hi), ratio_of(na.depth_hi, nb.depth_lo));
                     stable = passes(sup) == passes(inf) && passes(sup) == cond2;
                 }
-                if (!stable && std::getenv("SQUID_DEBUG_DEPTH"))
+                if (!stable && env_set("SQUID_DEBUG_DEPTH"))
                     std::fprintf(stderr, "depth-ambiguous edge (%d,%d) w=%d: a=[%g,%g,%g] b=[%g,%g,%g]\n", e.a, e.b, e.w, na.depth_lo, na.depth, na.depth_hi, nb.depth_lo, nb.depth, nb.depth_hi);
                 if (!stable) c->depth_ambiguous = true;
             }
@@ -703,7 +703,7 @@ int exact_breakpoints(sq_ctx* c, BPMap& bp) {
     for (size_t i = 0; i < all.size(); ++i) if (i == 0 || all[i].key != all[i - 1].key) grp.push_back(i);
     grp.push_back(all.size());
     const int ng = (int)grp.size() - 1;
-    static const bool prof = std::getenv("SQUID_BP_PROF") != nullptr;
+    static const bool prof = env_set("SQUID_BP_PROF");
     if (prof) std::fprintf(stderr, "exact_breakpoints: %zu hits in %d groups, %d pieces\n", all.size(), ng, np);
     std::vector<std::vector<std::pair<int, int>>> lists((size_t)ng);
     auto top = [&](int g) {

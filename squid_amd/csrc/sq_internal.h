@@ -26,6 +26,14 @@
 
 namespace sq {
 
+// ---------------------------------------------------------------------------------------------- environment switches
+// Every SQUID_* switch of the library is read through one of these four ("Environment switches", has the table of names).
+// A caller that wants the value once per process keeps it in a `static const`; one that tests flip inside a process calls per use.
+inline bool env_set(const char* name) { return std::getenv(name) != nullptr; }                                                        // present, whatever the value
+inline long long env_int(const char* name, long long dflt) { const char* v = std::getenv(name); return v ? std::atoll(v) : dflt; }  // integer with a default
+inline bool env_on(const char* name) { return env_int(name, 1) != 0; }                                                                // on unless "0"
+inline bool env_nonzero(const char* name) { return env_int(name, 0) != 0; }                                                           // off unless non-zero
+
 // ---------------------------------------------------------------------------------------------- host model
 // one aligned block of a chimeric fragment (host side is AoS: N_x is ~1 % of N_c)
 struct Blk {
@@ -353,7 +361,7 @@ struct HostClock {  // wall clock of a host stage into the context's timing tabl
     ~HostClock() {
         const auto t1 = std::chrono::steady_clock::now();
         c->timer.add(name, std::chrono::duration<double, std::milli>(t1 - t0).count());
-        static const bool trace = std::getenv("SQUID_HOST_TRACE") != nullptr;  // one line per stage: start (since the first stage of the process) and length
+        static const bool trace = env_set("SQUID_HOST_TRACE");  // one line per stage: start (since the first stage of the process) and length
         if (trace) {
             static const std::chrono::steady_clock::time_point origin = t0;
             std::fprintf(stderr, "[host %10.3f ms] %-28s %8.3f ms\n", std::chrono::duration<double, std::milli>(t0 - origin).count(), name, std::chrono::duration<double, std::milli>(t1 - t0).count());

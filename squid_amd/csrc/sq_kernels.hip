@@ -231,7 +231,6 @@ struct DeviceRecords {
     uint32_t h_slots = 1u << 16;
     DBuf<int32_t> ord_e, ord_o, ord_v;  // ordering kernel: packed input, packed output, values
     DBuf<int32_t> ord_me, ord_mo;       // k_order_mid: packed input, packed output
-    DBuf<unsigned long long> tok_prof;  // SQUID_TOK_PROF
     DBuf<int32_t> g_i, g_x;             // K6 / K7 (sq_graph_kernels.inc): graph ints + scratch, CSR / neighbour scratch
     DBuf<double> g_d;
     DBuf<uint8_t> g_b;
@@ -2777,9 +2776,7 @@ __global__ __launch_bounds__(64) void k_lz_resolve5(const uint32_t* tok, const i
     const bool ok = rsv::resolve_block<RS_STAGE>(tok + blk.toff, ntok[blockIdx.x], outbuf + (blk.uoff - out_base), blk.isize, (wv::lds_u8*)st_mem);  // (sq_resolve.inc)
     if (!ok && threadIdx.x == 0) atomicOr(&flags[0], 512);
 }
-// (experiment: SQUID_RESOLVE_LDS=<bytes> of unused dynamic LDS per resolve wave = a cap on the waves a CU holds -- 160 KB / bytes)
-static bool resolve_staged() { return std::getenv("SQUID_RESOLVE_STAGED") == nullptr || std::atoi(std::getenv("SQUID_RESOLVE_STAGED")) != 0; }  // (the default; 0: k_lz_resolve3.  Read per call: tests switch it)
-static unsigned resolve_lds_pad() { static const unsigned v = std::getenv("SQUID_RESOLVE_LDS") ? (unsigned)std::atoi(std::getenv("SQUID_RESOLVE_LDS")) : 0u; return v; }
+static bool resolve_staged() { return env_on("SQUID_RESOLVE_STAGED"); }  // (the default; 0: k_lz_resolve3.  Read per call: tests switch it)
 __global__ __launch_bounds__(64) void k_lz_resolve3(const uint32_t* tok, const int32_t* ntok, const InflBlock* blocks, int nblocks, unsigned long long out_base, uint8_t* outbuf, int32_t* flags) {
     const int lane = threadIdx.x;
     const InflBlock blk = blocks[blockIdx.x];
@@ -3171,7 +3168,7 @@ static int h2d_parallel(sq_ctx* c, uint8_t* dst, const uint8_t* src, size_t n) {
     DeviceRecords& D = *c->dev;
     constexpr int T = DeviceRecords::H2D_THREADS;
     constexpr size_t CH = (size_t)16 << 20;
-    if (n < 8 * CH || std::getenv("SQUID_H2D_SERIAL")) { HIPCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice)); return SQ_OK; }
+    if (n < 8 * CH) { HIPCHK(hipMemcpy(dst, src, n, hipMemcpyHostToDevice)); return SQ_OK; }
     std::lock_guard<std::mutex> lk(D.h2d_mu);
     for (int t = 0; t < T; ++t) {
         if (!D.h2d_stream[t]) HIPCHK(hipStreamCreateWithFlags(&D.h2d_stream[t], hipStreamNonBlocking));
@@ -3218,7 +3215,7 @@ static int h2d_parallel(sq_ctx* c, uint8_t* dst, const uint8_t* src, size_t n) {
 // batch one blocking copy by four threads in front of the batch's token pass -- 390 ms per C3 step where the same step from a
 // copy already in HBM takes 256.
 struct FileFeeder {
-    const size_t P = std::getenv("SQUID_FEED_PIECE_MB") ? (size_t)std::max(1, std::atoi(std::getenv("SQUID_FEED_PIECE_MB"))) << 20 : (size_t)8 << 20;  // a piece
+    const size_t P = (size_t)std::max(1, (int)env_int("SQUID_FEED_PIECE_MB", 8)) << 20;  // a piece
     sq_ctx* c;
     DeviceRecords& D;
     int fd = -1, T = 0;
@@ -3256,7 +3253,7 @@ struct FileFeeder {
         hi = std::min(file_n, upto);
         if (hi <= lo) return fail(c, SQ_E_ARG, "internal: empty file range");
         npieces = (hi - lo + P - 1) / P;
-        static const int env_t = std::getenv("SQUID_FEED_THREADS") ? std::atoi(std::getenv("SQUID_FEED_THREADS")) : 0;
+        static const int env_t = (int)env_int("SQUID_FEED_THREADS", 0);
         T = env_t > 0 ? env_t : usable_cpus() / std::max(1, c->P.world_size);  // (the rank's share of the CPUs the process may really use: cgroup quota, not the CPUs it can see)
         // (while the pairing of a large chimeric BAM runs on the host threads -- sq_ingest_files, the chimeric records came through this
         // reader just before -- the file is not what the step waits for and the readers only take CPU time from what it does wait for:
@@ -3359,7 +3356,7 @@ struct FileFeeder {
         for (;;) {
             const size_t j = next.fetch_add(1);
             if (j >= npieces || abort.load() || failed.load()) break;
-            static const long fail_at = std::getenv("SQUID_FEED_FAIL_AT") ? std::atol(std::getenv("SQUID_FEED_FAIL_AT")) : -1;  // (tests: a read error at that piece)
+            static const long fail_at = (long)env_int("SQUID_FEED_FAIL_AT", -1);  // (tests: a read error at that piece)
             if (fail_at >= 0 && (long)j == fail_at) { fail_with("cannot read the bamfile (injected by SQUID_FEED_FAIL_AT)"); break; }
             const size_t off = lo + j * P, len = std::min(P, hi - off);
             auto tk = std::chrono::steady_clock::now();
@@ -3407,7 +3404,7 @@ struct FileFeeder {
         // every few microseconds kept the runtime's lock busy for the thread that launches the kernels)
         // few copies queued at a time: the small device -> host read-backs of the batch loop (flags, record counts) travel on the same DMA
         // engines, and every 8 MiB piece queued in front of one of them is 160 us of waiting for the thread that drives the pipeline
-        static const size_t max_inflight = std::getenv("SQUID_FEED_INFLIGHT") ? (size_t)std::max(1, std::atoi(std::getenv("SQUID_FEED_INFLIGHT"))) : 8;
+        static const size_t max_inflight = (size_t)std::max(1, (int)env_int("SQUID_FEED_INFLIGHT", 8));
         std::deque<int> inflight[NS];
         std::deque<int> waiting;  // filled, not yet queued
         size_t done = 0, rr = 0, n_inflight = 0;
@@ -3651,7 +3648,7 @@ static int parse_device(sq_ctx* c, const uint8_t* d_bam, size_t nbytes, const un
       const ParseOut O{D.refid.p + n0, D.pos.p + n0, D.mrefid.p + n0, D.mpos.p + n0, D.endpos.p + n0, D.flag.p + n0, D.totlen.p + n0, D.mapq.p + n0, D.aux.p + n0, D.chim_slot_of.p + n0, D.parse_nblk.p, D.parse_first2.p};
       // (staging size by the mean record length of the chunk -- the bytes in front of its first record count in, which only errs towards the larger size)
       const double need = 64.0 * 1.08 * (double)nbytes / (double)n_rec + 64.0;
-      static const int force = std::getenv("SQUID_PARSE_LDS_KB") ? std::atoi(std::getenv("SQUID_PARSE_LDS_KB")) : 0;  // (tests: 18 / 22 / 28 / 40 / 63)
+      static const int force = (int)env_int("SQUID_PARSE_LDS_KB", 0);  // (tests: 18 / 22 / 28 / 40 / 63)
       const int kb = force ? force : need <= PARSE_LDS ? 18 : need <= 22528 ? 22 : need <= 28672 ? 28 : need <= 40960 ? 40 : 63;
       if (kb <= 18) hipLaunchKernelGGL(k_parse_records<PARSE_LDS>, grid_for(n_rec, PARSE_THREADS), dim3(PARSE_THREADS), 0, s, d_bam, nbytes, d_off, n_rec, C, P, O, fl);
       else if (kb <= 22) hipLaunchKernelGGL(k_parse_records<22528>, grid_for(n_rec, PARSE_THREADS), dim3(PARSE_THREADS), 0, s, d_bam, nbytes, d_off, n_rec, C, P, O, fl);
@@ -3752,10 +3749,6 @@ int dev_token_bench(sq_ctx* c, const char* path, int variant, int max_blocks, in
             case 25611: launch_inflate_spec<256, 11>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
             case 38411: launch_inflate_spec<384, 11>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
             case 38410: launch_inflate_spec<384, 10>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
-            case 35210: launch_inflate_spec<352, 10>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
-            case 41610: launch_inflate_spec<416, 10>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
-            case 44810: launch_inflate_spec<448, 10>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
-            case 38409: launch_inflate_spec<384, 9>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
             case 32010: launch_inflate_spec<320, 10>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
             case 19210: launch_inflate_spec<192, 10>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
             case 102411: launch_inflate_spec<1024, 11>(s, d_in.p, d_tab.p, nb, d_flags.p, d_tok.p, d_ntok.p); break;
@@ -3767,7 +3760,7 @@ int dev_token_bench(sq_ctx* c, const char* path, int variant, int max_blocks, in
         }
         HIPCHK(hipEventRecord(e1, s));
         if (resolve_staged()) hipLaunchKernelGGL(k_lz_resolve5, dim3(nb), dim3(64), 0, s, d_tok.p, d_ntok.p, d_tab.p, nb, 0ull, d_out.p, d_flags.p + 4);
-        else hipLaunchKernelGGL(k_lz_resolve3, dim3(nb), dim3(64), resolve_lds_pad(), s, d_tok.p, d_ntok.p, d_tab.p, nb, 0ull, d_out.p, d_flags.p + 4);
+        else hipLaunchKernelGGL(k_lz_resolve3, dim3(nb), dim3(64), 0, s, d_tok.p, d_ntok.p, d_tab.p, nb, 0ull, d_out.p, d_flags.p + 4);
         HIPCHK(hipEventRecord(e2, s));
         HIPCHK(hipStreamSynchronize(s));
         float a = 0, b = 0;
@@ -3830,35 +3823,33 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
     }
     const int64_t n_save = D.n, nb_save = D.nb;
     auto give_up = [&]() { (void)hipDeviceSynchronize(); D.n = n_save; D.nb = nb_save; D.r_pack_n = std::min(D.r_pack_n, n_save); c->counts.n_concordant = D.n; c->counts.n_blocks = D.nb; return 2; };
-    const bool report = std::getenv("SQUID_INGEST_TIMING") != nullptr, check = std::getenv("SQUID_INFLATE_CHECK") != nullptr;
-    const auto w0 = std::chrono::steady_clock::now();
-    auto since_ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    // ---- the reader's settings, all read here ("Environment switches"; per call unless `static`: the tests switch them inside one process)
+    const bool report = env_set("SQUID_INGEST_TIMING"), check = env_set("SQUID_INFLATE_CHECK");
+    // round 6: the token pass as one wave per BGZF block (k_inflate_spec, sq_inflate_spec.inc); SQUID_TOK_SPEC=0 runs the lane-per-block pass
+    const bool tok_spec = env_on("SQUID_TOK_SPEC");
     // a batch = 256 waves of the token pass (1 GiB inflated); five batches fill the 1280 token slots of the machine (five waves per CU).
     // Measured at C3 (round 4, eight sets): 512 MB 157 ms per step, 640 MB 141, 768 MB 137, 1 GiB 136, 1.25 GB 135
     // (round 6, wave-per-block token pass: a launch is over in a few milliseconds whatever its size, so the batches are as small as the chain
     // behind them -- resolve, boundaries, parse -- allows: 512 MB; from the page cache 156-161 ms per C3 step against 170-198 with 1 GiB)
-    const bool tok_spec_early = std::getenv("SQUID_TOK_SPEC") == nullptr || std::atoi(std::getenv("SQUID_TOK_SPEC")) != 0;
-    unsigned long long cap = std::getenv("SQUID_TOK_CAP_MB") ? (unsigned long long)std::atoll(std::getenv("SQUID_TOK_CAP_MB")) << 20 : (tok_spec_early ? 128ull : 256ull) * 64 * 65536;  // (made smaller below for a short range)
-    if (report) std::fprintf(stderr, "GPU ingest: entry + %.1f ms: device chosen, memory asked about\n", since_ms(w_entry));
-    HIPCHK(hipFuncSetAttribute((const void*)k_lz_resolve2, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 16));
-    HIPCHK(hipFuncSetAttribute((const void*)k_inflate_tok2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * (int)T2_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute((const void*)k_inflate_tok2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * (int)T2_LDS_BYTES));
+    const bool cap_given = env_set("SQUID_TOK_CAP_MB");
+    unsigned long long cap = cap_given ? (unsigned long long)env_int("SQUID_TOK_CAP_MB", 0) << 20 : (tok_spec ? 128ull : 256ull) * 64 * 65536;  // (made smaller below for a short range)
     // token waves per workgroup (SQUID_TOK_WPB, measured in DESIGN.md): 1 with the LDS-free resolve -- five single-wave workgroups per CU --;
     // with the LDS resolve 3 (93 KB), which leave the 64 KB slot of a resolve workgroup free on every CU
-    static const bool resolve_global = std::getenv("SQUID_RESOLVE_GLOBAL") == nullptr || std::atoi(std::getenv("SQUID_RESOLVE_GLOBAL")) != 0;  // k_lz_resolve3 (no LDS window); 0: k_lz_resolve2
-    static const int tok_wpb = std::getenv("SQUID_TOK_WPB") ? std::max(1, std::min(5, std::atoi(std::getenv("SQUID_TOK_WPB")))) : (resolve_global ? 1 : 3);
-    // round 6: the token pass as one wave per BGZF block (k_inflate_spec, sq_inflate_spec.inc); SQUID_TOK_SPEC=0 runs the lane-per-block pass
-    const bool tok_spec = std::getenv("SQUID_TOK_SPEC") == nullptr || std::atoi(std::getenv("SQUID_TOK_SPEC")) != 0;
-    static const bool tok_prof = std::getenv("SQUID_TOK_PROF") != nullptr;
-    if (tok_prof) HIPCHK(D.tok_prof.reserve(8 * 4096));
+    static const bool resolve_global = env_on("SQUID_RESOLVE_GLOBAL");  // k_lz_resolve3 (no LDS window); 0: k_lz_resolve2
+    static const int tok_wpb = env_set("SQUID_TOK_WPB") ? std::max(1, std::min(5, (int)env_int("SQUID_TOK_WPB", 0))) : (resolve_global ? 1 : 3);
     // (buffer sets in flight: the lane-per-block pass wants eight -- 1280 token waves resident --, the wave-per-block pass fills the machine from one
     // launch: three sets keep the token pass a batch or two ahead of the resolve)
-    const int il_depth = std::getenv("SQUID_IL_DEPTH") ? std::max(2, std::min((int)DeviceRecords::IL_DEPTH_MAX, std::atoi(std::getenv("SQUID_IL_DEPTH")))) : (tok_spec ? 3 : (resolve_global ? 8 : 5));
-    D.il_depth = il_depth;
+    const int il_depth = env_set("SQUID_IL_DEPTH") ? std::max(2, std::min((int)DeviceRecords::IL_DEPTH_MAX, (int)env_int("SQUID_IL_DEPTH", 0))) : (tok_spec ? 3 : (resolve_global ? 8 : 5));
     // The resolve of a batch writes at a fixed place of the set's inflated buffer, `room` bytes in: the incomplete record the batch in front
     // ends with (known only when that batch's boundaries are) is copied in front of it afterwards.  A longer tail -- a single record of more
     // than a megabyte -- moves the batch to a buffer of its own (PostSet::big).  SQUID_CARRY_ROOM=<bytes, a multiple of 16> (tests: 64 takes nearly every batch that way).
-    const unsigned long long room = std::getenv("SQUID_CARRY_ROOM") ? ((unsigned long long)std::max(0ll, std::atoll(std::getenv("SQUID_CARRY_ROOM"))) + 15) / 16 * 16 : (unsigned long long)1 << 20;
+    const unsigned long long room = env_set("SQUID_CARRY_ROOM") ? ((unsigned long long)std::max(0ll, env_int("SQUID_CARRY_ROOM", 0)) + 15) / 16 * 16 : (unsigned long long)1 << 20;
+    const auto w0 = std::chrono::steady_clock::now();
+    auto since_ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    if (report) std::fprintf(stderr, "GPU ingest: entry + %.1f ms: device chosen, memory asked about\n", since_ms(w_entry));
+    HIPCHK(hipFuncSetAttribute((const void*)k_lz_resolve2, hipFuncAttributeMaxDynamicSharedMemorySize, 65536 + 16));
+    HIPCHK(hipFuncSetAttribute((const void*)k_inflate_tok2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 5 * (int)T2_LDS_BYTES));
+    D.il_depth = il_depth;
     // the stream and the events of a buffer set are made when its first batch is staged (on the planner thread): a stream of a priority
     // level that has none yet costs the runtime a hardware queue, 7-8 ms each in a process that has just started -- eight of them in
     // front of the first batch were 60 ms of a cold start
@@ -3869,10 +3860,7 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
             // of the batch in front (library stream) should get the CUs that come free first
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-            static const bool spread = std::getenv("SQUID_IL_SPREAD") != nullptr && std::atoi(std::getenv("SQUID_IL_SPREAD")) != 0;
-            static const int tok_prio = std::getenv("SQUID_TOK_PRIO") ? std::atoi(std::getenv("SQUID_TOK_PRIO")) : 0;  // 0: lowest (default), 1: the library stream's, 2: highest
-            const int prio = tok_prio == 1 ? 0 : tok_prio == 2 ? hi : (spread && qi >= 4 ? (lo + hi) / 2 : lo);  // (experiment: the runtime keeps a pool of hardware queues per priority level)
-            if (hipStreamCreateWithPriority(&q, hipStreamNonBlocking, prio) != hipSuccess) { (void)hipGetLastError(); if (hipStreamCreate(&q) != hipSuccess) return (int)SQ_E_HIP; }
+            if (hipStreamCreateWithPriority(&q, hipStreamNonBlocking, lo) != hipSuccess) { (void)hipGetLastError(); if (hipStreamCreate(&q) != hipSuccess) return (int)SQ_E_HIP; }
         }
         DeviceRecords::InflSet& st = D.il_set[qi];
         if (!st.ready && hipEventCreateWithFlags(&st.ready, hipEventDisableTiming) != hipSuccess) return (int)SQ_E_HIP;
@@ -3914,20 +3902,18 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
             const size_t at = plan_at;
             // the first batches are small, so that the GPU has work after a few milliseconds of index walk and copy
             // (no ramp when the file is in HBM already: small batches only leave CUs empty for the length of a token wave)
-            static const unsigned long long ramp_env = std::getenv("SQUID_TOK_RAMP_MB") ? (unsigned long long)std::atoll(std::getenv("SQUID_TOK_RAMP_MB")) : 0;
-            const unsigned long long ramp0 = ramp_env ? ramp_env : (c->ingest_dfile ? 1024 : 128);
+            const unsigned long long ramp0 = c->ingest_dfile ? 1024 : 128;
             const unsigned long long ramp = ramp0 << (20 + std::min<size_t>(batches.size(), 8));
             unsigned long long bcap = std::min(cap, ramp);
             // (the end of the range in smaller batches: what stands behind the last byte is one batch's way through token pass, resolve, boundaries and parse)
-            // (While the block index is still being walked the rest of the range is an estimate from the file's size; SQUID_TOK_TAPER=0: only with a
-            // full index, as until round 6.  Measured and dropped: batches that keep shrinking to 16 MB -- twelve more batches per C3 step, each with its
+            // (While the block index is still being walked the rest of the range is an estimate from the file's size; until round 6 only with a
+            // full index.  Measured and dropped: batches that keep shrinking to 16 MB -- twelve more batches per C3 step, each with its
             // trip through the boundary chain: staged 94 -> 102 ms.)
-            static const bool taper = std::getenv("SQUID_TOK_TAPER") == nullptr || std::atoi(std::getenv("SQUID_TOK_TAPER")) != 0;
-            if (tok_spec_early && at < blocks.size()) {
+            if (tok_spec && at < blocks.size()) {
                 const size_t stop0 = more_blocks || b1 == (size_t)-1 ? blocks.size() : std::min(b1, blocks.size());
                 unsigned long long left = ~0ull;
                 if (!more_blocks) { if (stop0 > at) left = blocks[stop0 - 1].uoff + blocks[stop0 - 1].isize - blocks[at].uoff; }
-                else if (taper && at > b0 && file_bytes) {
+                else if (at > b0 && file_bytes) {
                     const BgzfRange &f = blocks[b0], &a = blocks[at];
                     const double ratio = (double)(a.uoff - f.uoff) / (double)std::max<unsigned long long>(1, a.coff - f.coff);
                     const unsigned long long end_c = (src && src->stop != (size_t)-1) ? std::min<unsigned long long>(src->stop, file_bytes) : (unsigned long long)file_bytes;
@@ -3962,7 +3948,7 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
     // A short range -- a chromosome shard of an eight-rank run holds an eighth of the file -- is cut into as many batches as a whole file, so that
     // the stages behind the token pass overlap as they do there: with 512 MB batches such a shard was three batches that went through the pipeline
     // nearly one after the other (tools/shard_project.py: 36-55 ms per rank where 21 would be its share).
-    if (tok_spec_early && !std::getenv("SQUID_TOK_CAP_MB")) {
+    if (tok_spec && !cap_given) {
         unsigned long long est = range_bytes_estimate();
         if (index_more && src && src->stop != (size_t)-1) {
             std::lock_guard<std::mutex> lk(bm);
@@ -4023,8 +4009,7 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
             launch_inflate_spec<SPEC_CH, SPEC_PB>(sa, st.src, st.tab.p, nb, st.flags.p, st.tok.p, st.ntok.p);
         } else {   // k_inflate_tok2 stays on the set's own stream: the token kernels of up to four batches run side by side
             EvTimer t1(c, "k_inflate_tok2", (double)B.cbytes + (double)B.bbytes * 2, sa);
-            if (tok_prof && k == 8) hipLaunchKernelGGL(k_inflate_tok2<true>, dim3((nb + 63) / 64), dim3(64), T2_LDS_BYTES, sa, st.src, st.tab.p, nb, st.flags.p, st.tok.p, st.ntok.p, st.lens.p, D.tok_prof.p);
-            else hipLaunchKernelGGL(k_inflate_tok2<false>, dim3(((nb + 63) / 64 + tok_wpb - 1) / tok_wpb), dim3(64 * tok_wpb), tok_wpb * T2_LDS_BYTES, sa, st.src, st.tab.p, nb, st.flags.p, st.tok.p, st.ntok.p, st.lens.p, nullptr);
+            hipLaunchKernelGGL(k_inflate_tok2<false>, dim3(((nb + 63) / 64 + tok_wpb - 1) / tok_wpb), dim3(64 * tok_wpb), tok_wpb * T2_LDS_BYTES, sa, st.src, st.tab.p, nb, st.flags.p, st.tok.p, st.ntok.p, st.lens.p, nullptr);
         }
         // the resolve, right behind: into the set's inflated buffer, which batch k - depth has left -- its parse is over (the planner waits for
         // that iteration of the batch loop) and its tail has been copied in front of the batch behind it (`carried`)
@@ -4034,7 +4019,7 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
         {
             EvTimer t2(c, resolve_global ? (resolve_staged() ? "k_lz_resolve5" : "k_lz_resolve3") : "k_lz_resolve2", (double)B.bbytes * 3, sa);
             if (resolve_global && resolve_staged()) hipLaunchKernelGGL(k_lz_resolve5, dim3(nb), dim3(64), 0, sa, st.tok.p, st.ntok.p, st.tab.p, nb, B.bbase, P.out.p + room, st.flags.p);
-            else if (resolve_global) hipLaunchKernelGGL(k_lz_resolve3, dim3(nb), dim3(64), resolve_lds_pad(), sa, st.tok.p, st.ntok.p, st.tab.p, nb, B.bbase, P.out.p + room, st.flags.p);
+            else if (resolve_global) hipLaunchKernelGGL(k_lz_resolve3, dim3(nb), dim3(64), 0, sa, st.tok.p, st.ntok.p, st.tab.p, nb, B.bbase, P.out.p + room, st.flags.p);
             else hipLaunchKernelGGL(k_lz_resolve2, dim3(nb), dim3(128), 65536 + 16, sa, st.tok.p, st.ntok.p, st.tab.p, nb, B.bbase, P.out.p + room, st.flags.p);
         }
         HIPCHK(hipEventRecord(st.ready, sa));
@@ -4095,10 +4080,9 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
     if (!D.il_parse_stream) {
         // (highest priority: the parse of batch k shares the machine with the resolves and token passes of the batches behind -- thousands of
         // one-wave workgroups that take every free wave slot -- and the batch loop waits for the parse)
-        static const bool parse_hi = std::getenv("SQUID_PARSE_PRIO") == nullptr || std::atoi(std::getenv("SQUID_PARSE_PRIO")) != 0;
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (!parse_hi || hipStreamCreateWithPriority(&D.il_parse_stream, hipStreamNonBlocking, hi) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipStreamCreateWithFlags(&D.il_parse_stream, hipStreamNonBlocking)); }
+        if (hipStreamCreateWithPriority(&D.il_parse_stream, hipStreamNonBlocking, hi) != hipSuccess) { (void)hipGetLastError(); HIPCHK(hipStreamCreateWithFlags(&D.il_parse_stream, hipStreamNonBlocking)); }
     }
     if (!D.il_host) HIPCHK(hipHostMalloc((void**)&D.il_host, 64 * sizeof(int32_t)));
     hipStream_t sp = D.il_parse_stream;
@@ -4218,16 +4202,6 @@ int dev_ingest_bgzf(sq_ctx* c, const uint8_t* file, std::vector<BgzfRange>& bloc
         src->streamed = true;
         if (feed->walk) { std::lock_guard<std::mutex> lk(feed->mu); src->walk_p = feed->end_state.p; src->walk_total = feed->end_state.total; src->bad = feed->walk_bad; }
     }
-    if (tok_prof && batches.size() > 8) {  // (batch 8 ran the instrumented kernel)
-        const int nw = (int)((batches[8].end - batches[8].at + 63) / 64);
-        std::vector<unsigned long long> hp(8 * (size_t)nw);
-        HIPCHK(hipMemcpy(hp.data(), D.tok_prof.p, hp.size() * 8, hipMemcpyDeviceToHost));
-        double sum[8] = {0};
-        for (int w = 0; w < nw; ++w) for (int q = 0; q < 8; ++q) sum[q] += (double)hp[8 * (size_t)w + q];
-        const double steps = sum[6] / nw;
-        std::fprintf(stderr, "token pass profile (batch 8, %d waves, %.0f steps per wave; s_memtime ticks per step): emit+header %.1f, header->topup-check %.1f, topup %.1f, ll decode %.1f, match path %.1f, loop/literal %.1f\n",
-                     nw, steps, sum[0] / sum[6], sum[1] / sum[6], sum[2] / sum[6], sum[3] / sum[6], sum[4] / sum[6], sum[7] / sum[6]);
-    }
     if (report) std::fprintf(stderr, "GPU ingest: first two batches queued after %.1f ms, all %zu batches through after %.1f ms (%.1f ms since entry; %llu MB per batch)\n", w_first, batches.size(), since_ms(w0), since_ms(w_entry), cap >> 20);
     return SQ_OK;
 }
@@ -4317,8 +4291,7 @@ int dev_upload_nodes(sq_ctx* c, const std::vector<Node>& nodes) {
 // Timing-only switches that cut a kernel short: never silently.  The pass still runs (the timers are what such a run is for), a line goes
 // to stderr, and sq_build_graph ends with SQ_E_ARG instead of handing out the graph made from the mutilated pass.
 static int ablate_switch(sq_ctx* c, const char* name) {
-    const char* v = std::getenv(name);
-    const int level = v ? std::atoi(v) : 0;
+    const int level = (int)env_int(name, 0);
     if (level) {
         if (!c->ablated) std::fprintf(stderr, "squid_hip: %s=%d cuts a kernel short (timing only): no graph, no SV calls from this run\n", name, level);
         c->ablated = true;
@@ -4332,7 +4305,7 @@ int dev_classify(sq_ctx* c, int32_t last_info[4]) {
     const int64_t n = D.n;
     RecView R = D.view();
     HIPCHK(D.cls.reserve(n + 4)); HIPCHK(D.keep.reserve(n + 4));
-    if (std::getenv("SQUID_CALIB")) {
+    if (env_set("SQUID_CALIB")) {
         const int64_t words = (int64_t)1 << 28;  // 1 GiB: larger than the 256 MiB Infinity Cache
         HIPCHK(D.calib.reserve(words));
         HIPCHK(hipMemsetAsync(D.calib.p, 1, words * 4, s));
@@ -4380,7 +4353,6 @@ int dev_pass1(sq_ctx* c, const std::vector<int32_t>& cl_chr, const std::vector<i
     HIPCHK(D.cl_bucket.reserve((size_t)n_ref + 1 + (size_t)std::max(cl_total, 1)));
     HIPCHK(hipMemcpy(D.cl_bucket.p, bo.data(), ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice));
     if (n == 0) return SQ_OK;
-    for (int32_t len : c->ref_len) (void)len;
     if (c->ref_len.size() >= ((size_t)1 << 30)) return fail(c, SQ_E_CAPACITY, "too many references");
     const int ntiles = (int)((n + P1_TILE - 1) / P1_TILE);
     ClusterView C{ncl, D.cl_chr.p, D.cl_chr.p + ncl, D.cl_chr.p + 2 * (size_t)ncl, n_ref, D.cl_bucket.p, D.cl_bucket.p + n_ref + 1};
@@ -4413,38 +4385,15 @@ int dev_pass1(sq_ctx* c, const std::vector<int32_t>& cl_chr, const std::vector<i
         A.trig = D.trig.p; A.rc_cluster = D.rc_cluster.p; A.rc_pos = D.rc_pos.p; A.rc_len = D.rc_len.p; A.rc_cap = (int)D.rc_cap;
         A.sc = D.p1_sc.p;
         {   // reads: 32 B of fixed fields per record (two 16-byte words) + its first and last block (16 B each); writes: class and keep byte
-            EvTimer t(c, SQ_P1W_ITEMS > 0 ? "k_pass1w" : "k_pass1", 32.0 * n + 16.0 * D.nb);
-#if SQ_P1W_ITEMS > 0
-            static const int p1_waves = std::getenv("SQUID_P1_WAVES") ? std::atoi(std::getenv("SQUID_P1_WAVES")) : (P1_ITEMS >= 4 ? 3 : 4);  // (measured at C3: four records per lane at three waves per SIMD 0.85 ms, two at four waves 0.98)
-            if (p1_waves == 4) hipLaunchKernelGGL((k_pass1w<4>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A);
-            else if (p1_waves == 3) hipLaunchKernelGGL((k_pass1w<3>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A);
-            else if (p1_waves == 5) hipLaunchKernelGGL((k_pass1w<5>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A);
-            else if (p1_waves == 6) hipLaunchKernelGGL((k_pass1w<6>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A);
-            else hipLaunchKernelGGL((k_pass1w<8>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A);
-#else
-            static const bool prof = std::getenv("SQUID_P1_PROF") != nullptr;  // s_memtime sums per section of a tile (thread 0 of every workgroup)
-            if (prof) {
-                HIPCHK(D.tok_prof.reserve(16)); HIPCHK(hipMemsetAsync(D.tok_prof.p, 0, 16 * 8, s));
-                hipLaunchKernelGGL((k_pass1<true, 4>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A, D.tok_prof.p);
-                unsigned long long hp[8];
-                HIPCHK(hipMemcpyAsync(hp, D.tok_prof.p, sizeof hp, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-                static const char* nm[7] = {"start", "load+classify+dedup", "scan", "clusters+z+triggers+rest", "run of slots", "emit", "-"};
-                for (int q = 0; q < 7; ++q) std::fprintf(stderr, "[k_pass1] %-28s %10.0f ticks per tile\n", nm[q], (double)hp[q] / (double)std::max<unsigned long long>(hp[7], 1));
-            } else {
-                static const int p1_waves = std::getenv("SQUID_P1_WAVES") ? std::atoi(std::getenv("SQUID_P1_WAVES")) : 5;  // (five waves per SIMD with 44 B of spills: 1.49 ms at C3; four without: 1.65; six: 2.49)
-                if (p1_waves == 5) hipLaunchKernelGGL((k_pass1<false, 5>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A, (unsigned long long*)nullptr);
-                else if (p1_waves == 6) hipLaunchKernelGGL((k_pass1<false, 6>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A, (unsigned long long*)nullptr);
-                else if (p1_waves == 8) hipLaunchKernelGGL((k_pass1<false, 8>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A, (unsigned long long*)nullptr);
-                else hipLaunchKernelGGL((k_pass1<false, 4>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A, (unsigned long long*)nullptr);
-            }
-#endif
+            EvTimer t(c, "k_pass1w", 32.0 * n + 16.0 * D.nb);
+            hipLaunchKernelGGL((k_pass1w<3>), dim3(ntiles), dim3(P1_THREADS), 0, s, R, C, A);  // (measured at C3: four records per lane at three waves per SIMD 0.85 ms, two at four waves 0.98)
         }
         {   // per tile: count 4 + pair 8 + two keys 16 in, rank 4 + pair 8 out
             EvTimer t(c, "k_tile_scan", 40.0 * ntiles);
             const int ngroups = (ntiles + TS_THREADS - 1) / TS_THREADS;
             HIPCHK(D.tile_part.reserve((size_t)ngroups + 1));
             hipLaunchKernelGGL(k_tile_partial, dim3(ngroups), dim3(TS_THREADS), 0, s, ntiles, D.tile_cnt.p, D.tile_ob.p, D.tile_max.p, D.tile_part.p);
-            hipLaunchKernelGGL(k_tile_scan, dim3(ngroups), dim3(TS_THREADS), 0, s, ntiles, D.tile_cnt.p, D.tile_ob.p, D.tile_first.p, D.tile_max.p, D.tile_part.p, D.tile_rank.p, D.tile_ob.p + ntiles, D.p1_sc.p, SQ_P1W_ITEMS > 0 ? D.tile_K.p : (const int32_t*)nullptr, D.trig.p);
+            hipLaunchKernelGGL(k_tile_scan, dim3(ngroups), dim3(TS_THREADS), 0, s, ntiles, D.tile_cnt.p, D.tile_ob.p, D.tile_first.p, D.tile_max.p, D.tile_part.p, D.tile_rank.p, D.tile_ob.p + ntiles, D.p1_sc.p, D.tile_K.p, D.trig.p);
             if (ncl) hipLaunchKernelGGL(k_trig_rank, dim3((ncl + 255) / 256), dim3(256), 0, s, ncl, ntiles, D.tile_rank.p, D.trig.p);
         }
         HIPCHK(hipMemcpyAsync(sc, D.p1_sc.p, sizeof sc, hipMemcpyDeviceToHost, s));
@@ -4518,7 +4467,7 @@ int dev_segment_support(sq_ctx* c, int ncl, long long seed, SegSupport& out) {
     int32_t run = (int32_t)k;
     for (int q = ncl - 1; q >= 0; --q) { if (ht[q] < run) run = ht[q]; out.trigger[q] = run; }
     D.h_tile_rank.assign(hk, hk + ntiles + 1);
-    if (std::getenv("SQUID_PREP_DEBUG")) std::fprintf(stderr, "[prepare] kept %lld zero-coverage records %d ConcordRest candidates %d clusters %d\n", (long long)k, nz, cnt, ncl);
+    if (env_set("SQUID_PREP_DEBUG")) std::fprintf(stderr, "[prepare] kept %lld zero-coverage records %d ConcordRest candidates %d clusters %d\n", (long long)k, nz, cnt, ncl);
     return SQ_OK;
 }
 
@@ -4658,23 +4607,15 @@ int dev_node_depth(sq_ctx* c, const std::vector<Node>& nodes, int64_t n_break, s
         unsigned int *t_agg = D.depth_tiles.p, *t_first = t_agg + ntiles, *t_front = t_first + ntiles;
         int32_t *t_flagged = (int32_t*)(t_front + ntiles), *n_flagged = D.flags.p + 7;  // (flags were just zeroed; read back with them)
         DepthTiles T{t_agg, t_first, n_flagged, t_flagged, t_front, ablate_switch(c, "SQUID_D2_ABLATE"), nullptr, nullptr};
-        static const bool fuse = ST_THREADS == 64 && !(std::getenv("SQUID_NO_FUSE") && std::atoi(std::getenv("SQUID_NO_FUSE")));
         D.p2_valid_n = -1;
-        if (fuse && D.r_pack_n >= n && n < 0xffffffffll) {
+        if (D.r_pack_n >= n && n < 0xffffffffll) {
             // k_pass2w: the depth sums of the tiles that lie inside one node AND the first pass of the edge stage, in one read of the records
             // (record rows 32 + keep 1 per record, first and last block 16 each); k_depth2 then sweeps only the tiles left on the list
             HIPCHK(D.p2_list.reserve((size_t)n)); HIPCHK(D.p2_words.reserve((size_t)ntiles + 4)); HIPCHK(D.bp_key.reserve((size_t)((n + 255) / 256) + 1));
             HIPCHK(hipMemsetAsync(D.p2_words.p, 0, 8, s));
-            P2Args A2{D.keep.p, D.r_break.p, T, a_mc, a_ms, a_oc, a_os, D.flags.p, stripes, D.p2_words.p + 2, D.p2_words.p + 1, D.bp_key.p, D.p2_list.p, D.p2_words.p, std::getenv("SQUID_EDGES_ALL") ? 1 : 0};
+            P2Args A2{D.keep.p, D.r_break.p, T, a_mc, a_ms, a_oc, a_os, D.flags.p, stripes, D.p2_words.p + 2, D.p2_words.p + 1, D.bp_key.p, D.p2_list.p, D.p2_words.p, env_set("SQUID_EDGES_ALL") ? 1 : 0};
             { EvTimer t(c, "k_pass2w", 33.0 * n + 32.0 * n);
-              static const int p2_waves = std::getenv("SQUID_P2_WAVES") ? std::atoi(std::getenv("SQUID_P2_WAVES")) : 6;  // (C3: 3 waves per SIMD 0.77 ms, 4 0.64, 5 0.56, 6 0.51)
-              if (p2_waves == 3) hipLaunchKernelGGL((k_pass2w<3>), dim3(ntiles), dim3(64), 0, s, R, nv, A2);
-              else if (p2_waves == 4) hipLaunchKernelGGL((k_pass2w<4>), dim3(ntiles), dim3(64), 0, s, R, nv, A2);
-              else if (p2_waves == 7) hipLaunchKernelGGL((k_pass2w<7>), dim3(ntiles), dim3(64), 0, s, R, nv, A2);
-              else if (p2_waves == 8) hipLaunchKernelGGL((k_pass2w<8>), dim3(ntiles), dim3(64), 0, s, R, nv, A2);
-              else if (p2_waves == 5) hipLaunchKernelGGL((k_pass2w<5>), dim3(ntiles), dim3(64), 0, s, R, nv, A2);
-              else if (p2_waves == 6) hipLaunchKernelGGL((k_pass2w<6>), dim3(ntiles), dim3(64), 0, s, R, nv, A2);
-              else hipLaunchKernelGGL((k_pass2w<6>), dim3(ntiles), dim3(64), 0, s, R, nv, A2); }
+              hipLaunchKernelGGL((k_pass2w<6>), dim3(ntiles), dim3(64), 0, s, R, nv, A2); }  // (C3: 3 waves per SIMD 0.77 ms, 4 0.64, 5 0.56, 6 0.51)
             D.p2_valid_n = n; D.bp_key_n = n;
             T.list = D.p2_words.p + 2; T.n_list = D.p2_words.p + 1;
             { EvTimer t(c, "k_depth2", 0);  // (the tiles k_pass2w left: their bytes are part of its read)
@@ -4750,7 +4691,7 @@ int dev_concordant_edges(sq_ctx* c, const std::vector<Node>& nodes, std::vector<
             HIPCHK(hipMemcpyAsync(count, D.p2_words.p, 4, hipMemcpyDeviceToDevice, s));
         } else {
             EvTimer t(c, "k_edges_near", 23.0 * n + 16.0 * D.nb);  // (+ pos 4 for the breakpoint-cursor keys)
-            hipLaunchKernelGGL(k_edges_near, grid_for(n, 256), dim3(256), 0, s, R, nv, D.keep.p, D.bp_key.p, list, count, std::getenv("SQUID_EDGES_ALL") ? 1 : 0);
+            hipLaunchKernelGGL(k_edges_near, grid_for(n, 256), dim3(256), 0, s, R, nv, D.keep.p, D.bp_key.p, list, count, env_set("SQUID_EDGES_ALL") ? 1 : 0);
         }
         D.bp_key_n = n;
         { EvTimer t(c, "k_edges", 0);
@@ -5022,8 +4963,7 @@ struct FChimHist { const uint32_t* h; __device__ int operator()(int64_t i) const
 
 // more soft fragments than this in one stage: the stage goes back to the host (SQUID_CHIM_SOFT_MAX: a debug bound, the tests force the fallback with 0)
 static uint32_t chim_soft_max() {
-    const char* v = std::getenv("SQUID_CHIM_SOFT_MAX");
-    return v ? (uint32_t)std::max(0l, std::atol(v)) : (1u << 20);
+    return (uint32_t)std::max(0ll, env_int("SQUID_CHIM_SOFT_MAX", 1 << 20));
 }
 
 // the fragment table: flattened on the host threads into one page-locked buffer, one copy.  From the untrimmed fragments (frags0).

@@ -62,6 +62,8 @@ typedef unsigned __int128 Mask;
 inline int mask_ctz(Mask m) { const uint64_t lo = (uint64_t)m; return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll((uint64_t)(m >> 64)); }
 inline bool mask_bit(Mask m, int i) { return (bool)((m >> i) & 1); }
 constexpr int HOST_NMAX = 128, SCC_MAX = 22;
+// SQUID_ORDER_BUDGET=<search nodes>: the bound of the exact host solver (fault injection: a small one makes it give up and keep the identity order)
+inline long order_budget_env() { static const long v = (long)env_int("SQUID_ORDER_BUDGET", 20000000); return v; }
 struct HostSolver {
     int n;
     const std::vector<LEdge>& E;
@@ -283,7 +285,7 @@ struct HostSolver {
     void run() {
         // depth-first over nodes n-1..0, forward before reversed; a branch must be able to beat the incumbent strictly
         // (the incumbent starts one below the greedy set's weight: the first orientation that reaches it is found, not assumed)
-        static const bool seed = std::getenv("SQUID_ORDER_NO_SEED") == nullptr;
+        static const bool seed = !env_set("SQUID_ORDER_NO_SEED");
         if (seed && n > 12) best = greedy_lower_bound() - 1;
         struct Fr { Mask mask; int k; };
         std::vector<Fr> st;
@@ -384,7 +386,7 @@ struct Builder {
         const int top = (int)tree.size();
         tree.push_back(TreeNode());
         std::vector<int> leaf_tnode;                   // leaf part id -> tree node
-        const bool simple_recursion = std::getenv("SQUID_MINCUT_SIMPLE") != nullptr;  // the one-traversal-per-split form (cross-check)
+        const bool simple_recursion = env_set("SQUID_MINCUT_SIMPLE");  // the one-traversal-per-split form (cross-check)
         if (simple_recursion) {
             struct Job { int root, tnode; };
             std::vector<Job> jobs(1, Job{0, top});
@@ -623,8 +625,7 @@ int order_components(sq_ctx* c) {
         for (const Edge& e : c->edges) if (e.a != e.b) cedge[(size_t)fe[c->label[e.a]]++] = e;
     }
     const int GPU_NMAX = 8;
-    static const long order_budget = std::getenv("SQUID_ORDER_BUDGET") ? std::atol(std::getenv("SQUID_ORDER_BUDGET")) : 20000000L;
-    static const bool order_host_mid = std::getenv("SQUID_ORDER_HOST_MID") != nullptr;  // debugging: 9..19 nodes on the host as well
+    const long order_budget = order_budget_env();
     struct Group {
         int k0 = 0, k1 = 0;
         Builder B;
@@ -658,7 +659,7 @@ int order_components(sq_ctx* c) {
             Piece& p = G.B.pieces[pi];
             const int pn = (int)p.ids.size();
             if (pn == 1) continue;
-            const bool small = pn <= GPU_NMAX, mid = !small && pn <= ORDER_MID_NMAX && !order_host_mid;
+            const bool small = pn <= GPU_NMAX, mid = !small && pn <= ORDER_MID_NMAX;
             if (!small && !mid) { G.large.push_back((int)pi); continue; }
             std::vector<int32_t>& e5 = small ? G.e5 : G.me5;
             SmallProblem sp{pn, (int)(e5.size() / 5), (int)p.edges.size()};
@@ -718,7 +719,7 @@ int order_components(sq_ctx* c) {
         }
     });
     t0 = std::chrono::steady_clock::now();
-    static const bool order_prof = std::getenv("SQUID_ORDER_PROF") != nullptr;
+    static const bool order_prof = env_set("SQUID_ORDER_PROF");
     std::atomic<long> unsolved{0};
     auto solve = [&](Piece& p) {
         const int pn = (int)p.ids.size();
@@ -801,7 +802,7 @@ int order_problem_debug(sq_ctx* c, int n, const std::vector<int32_t>& edges5, bo
     } else {
         std::vector<LEdge> E;
         for (size_t i = 0; i < edges5.size(); i += 5) E.push_back(LEdge{edges5[i], edges5[i + 1], edges5[i + 2] != 0, edges5[i + 3] != 0, edges5[i + 4]});
-        static const long order_budget = std::getenv("SQUID_ORDER_BUDGET") ? std::atol(std::getenv("SQUID_ORDER_BUDGET")) : 20000000L;
+        const long order_budget = order_budget_env();
         HostSolver hs(n, E, order_budget);
         hs.run();
         if (hs.failed || hs.best < 0) return fail(c, SQ_E_CAPACITY, "ordering problem beyond the exact solver's budget");

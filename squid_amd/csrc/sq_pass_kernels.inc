@@ -39,17 +39,9 @@ __global__ void k_last_info_raw(RecView R, int min_mapq, int32_t* out) {
     }
 }
 
-// SQ_P1W_ITEMS > 0 (default): pass 1 is k_pass1w -- ONE WAVE per tile of 64 * SQ_P1W_ITEMS records, no LDS, no barrier, the hot path
-// without branches; 0: the round-3/4 kernel k_pass1 (a workgroup of four waves per tile of 512 records), kept for A/B builds
-#ifndef SQ_P1W_ITEMS
-#define SQ_P1W_ITEMS 4
-#endif
-#if SQ_P1W_ITEMS > 0
-constexpr int P1_THREADS = 64, P1_ITEMS = SQ_P1W_ITEMS, P1_TILE = P1_THREADS * P1_ITEMS;
-#else
-constexpr int P1_THREADS = 256, P1_ITEMS = 2, P1_TILE = P1_THREADS * P1_ITEMS;
-#endif
-// scalar results of pass 1 (int32 slots of P1Args::sc); k_pass1 writes FLAGS / ZC / REST, k_tile_scan the others
+// pass 1 is k_pass1w -- ONE WAVE per tile of 64 * P1_ITEMS records, no LDS, no barrier, the hot path without branches
+constexpr int P1_THREADS = 64, P1_ITEMS = 4, P1_TILE = P1_THREADS * P1_ITEMS;
+// scalar results of pass 1 (int32 slots of P1Args::sc); k_pass1w writes FLAGS / ZC / REST, k_tile_scan the others
 enum { P1S_FLAGS = 0, P1S_KEPT = 1, P1S_ZC = 2, P1S_REST = 3, P1S_FIRST_REFID = 4, P1S_FIRST_POS = 5, P1S_OTHER_LO = 6, P1S_OTHER_HI = 7, P1S_WORDS = 8 };
 // bits of sc[P1S_FLAGS]
 enum { P1F_UNSORTED = 1, P1F_NEGATIVE_END = 2 };
@@ -215,360 +207,8 @@ __device__ __forceinline__ unsigned long long wave_maxscan_excl_u64(unsigned lon
     total = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)h, 63) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)l, 63);
     return ((unsigned long long)(uint32_t)dpp_shr1((int)h) << 32) | (uint32_t)dpp_shr1((int)l);  // (lane 0: 0)
 }
-#if SQ_P1W_ITEMS == 0
-template <bool PROF, int WAVES>  // WAVES: waves per SIMD the register allocation aims at (4: what the kernel needs without spilling)
-__global__ __launch_bounds__(P1_THREADS) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_pass1(RecView R, ClusterView C, P1Args A, unsigned long long* prof) {
-    unsigned long long tp[8];
-    if (PROF) tp[0] = tp[1] = __builtin_amdgcn_s_memtime();
-    constexpr int NW = P1_THREADS / 64, NS = P1_ITEMS * NW;  // stream order inside the tile = (item, wave, lane); NS slots of 64 records
-    __shared__ int s_cnt[NS];
-    __shared__ unsigned long long s_ob[NS];
-    __shared__ long long s_first[NS], s_last[NS];
-    __shared__ NKey s_key[NS];  // key of the last record of every 64
-    __shared__ int s_zbase;
-    __shared__ int s_zcnt[NS];
-    const int tile = blockIdx.x;  // tiles are independent of each other: what runs along the stream is put together by k_tile_scan / k_zfinal
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t tbase = (int64_t)tile * P1_TILE;
-    const unsigned long long ltmask = (1ull << lane) - 1;
-    // ---- loads, level by level, every load UNCONDITIONAL (indices clamped into the arrays; a load inside a per-lane branch is waited
-    // for before the next one is issued): the fixed fields; then the first and last block (CIGAR order) and the geometry of the
-    // record's chromosome in the cluster index; then the index entry; then the clusters around it
-    int refid[P1_ITEMS], pos[P1_ITEMS], mrefid[P1_ITEMS], mpos[P1_ITEMS], flag[P1_ITEMS], totlen[P1_ITEMS], mapq[P1_ITEMS], aux[P1_ITEMS];
-    uint32_t bo[P1_ITEMS], bo1[P1_ITEMS];
-    bool live[P1_ITEMS];
-#pragma unroll
-    for (int i = 0; i < P1_ITEMS; ++i) {
-        const int64_t r = tbase + i * P1_THREADS + tid;
-        live[i] = r < R.n;
-        const int64_t rc = live[i] ? r : R.n - 1;  // (the grid exists only for R.n > 0)
-        // the whole fixed part of the record in two 16-byte loads (r_pack: k_pack_records), not ten narrow ones from ten arrays
-        const int4 w0 = R.r_pack[2 * rc], w1 = R.r_pack[2 * rc + 1];
-        refid[i] = w0.x; pos[i] = w0.y; mrefid[i] = w0.z; mpos[i] = w0.w;
-        flag[i] = (int)((uint32_t)w1.x & 0xffffu); totlen[i] = (int)((uint32_t)w1.x >> 16);
-        mapq[i] = (int)((uint32_t)w1.y & 0xffu); aux[i] = (int)(((uint32_t)w1.y >> 8) & 0xffu);
-        bo[i] = (uint32_t)w1.z; bo1[i] = bo[i] + ((uint32_t)w1.y >> 16);
-    }
-    int4 qa[P1_ITEMS], qb[P1_ITEMS];
-    {
-        uint32_t ia[P1_ITEMS], ib[P1_ITEMS];
-#pragma unroll
-        for (int i = 0; i < P1_ITEMS; ++i) {
-            const int nblk = (int)(bo1[i] - bo[i]);
-            ia[i] = nblk > 0 ? bo[i] : 0; ib[i] = nblk > 1 ? bo1[i] - 1 : ia[i];
-            qa[i] = make_int4(0, 0, 0, 0); qb[i] = qa[i];
-        }
-        if (R.nb > 0) {  // (uniform)
-#pragma unroll
-            for (int i = 0; i < P1_ITEMS; ++i) qa[i] = R.b_pack[ia[i]];
-#pragma unroll
-            for (int i = 0; i < P1_ITEMS; ++i) qb[i] = R.b_pack[ib[i]];
-        }
-#pragma unroll
-        for (int i = 0; i < P1_ITEMS; ++i) if (bo1[i] == bo[i]) { qa[i] = make_int4(0, 0, 0, 0); qb[i] = qa[i]; }
-    }
-    if (A.ablate == 1) {
-#pragma unroll
-        for (int i = 0; i < P1_ITEMS; ++i) if (live[i]) A.cls[tbase + i * P1_THREADS + tid] = (uint8_t)(refid[i] ^ pos[i] ^ mrefid[i] ^ mpos[i] ^ flag[i] ^ totlen[i] ^ mapq[i] ^ aux[i] ^ qa[i].x ^ qb[i].y ^ qa[i].z);
-        return;
-    }
-    // ---- clusters passed (SegmentGraph.cpp:353: #clusters with (chr, right) < (RefID, position)).  The stream is sorted, so the answers
-    // for the tile's first and last record bracket everybody's, and nearly always they are the same: those two are looked up with
-    // uniform (scalar) loads at the start, far ahead of their use; a record whose key does not lie between the two keys (an unsorted
-    // stretch of filtered-out records) or a tile that a cluster ends in takes the per-record lookup
-    const bool have_cl = C.n > 0;  // (uniform)
-    bool t_uni = false;
-    int t_K = 0, t_dc = 0, t_dr = 0, t_uc = 0, t_us = 0, t_ur = 0;  // clusters passed; the cluster in front (chr, right) and the one at that position (chr, start, right)
-    long long t_key0 = 0, t_key1 = 0;
-    if (have_cl) {
-        const int64_t ra = tbase, rb = (tbase + P1_TILE < R.n ? tbase + P1_TILE : R.n) - 1;
-        const int ref_a = R.refid[ra], pos_a = R.pos[ra], ref_b = R.refid[rb], pos_b = R.pos[rb];
-        t_key0 = sort_key(ref_a, pos_a); t_key1 = sort_key(ref_b, pos_b);
-        if (ref_a >= 0 && ref_a < C.n_ref && ref_b >= 0 && ref_b < C.n_ref && t_key0 <= t_key1) {
-            const int K0 = clusters_passed_idx(C, ref_a, pos_a), K1 = clusters_passed_idx(C, ref_b, pos_b);
-            if (K0 == K1) {
-                t_uni = true; t_K = K0;
-                if (K0 > 0) { t_dc = C.chr[K0 - 1]; t_dr = C.right[K0 - 1]; }
-                if (K0 < C.n) { t_uc = C.chr[K0]; t_us = C.start[K0]; t_ur = C.right[K0]; }  // (zero sentinel after the last cluster, ledger B21)
-            }
-        }
-    }
-    // the record in front of the tile (the other records take their predecessor from the lane below, lane 0 from the last lane of
-    // the 64 records in front through LDS)
-    NKey k_front = nkey_empty();
-    k_front.bits = 1;  // (no filter bit: nothing precedes the first record)
-    if (tid == 0 && tbase > 0 && tbase < R.n) k_front = nkey_at(R, tbase - 1, A.min_mapq);
-    // ---- classification (SegmentGraph.cpp:297-303,651-683,1579-1585,3131-3142) and the key ReadRec_t::Equal looks at
-    uint8_t cl[P1_ITEMS], kp[P1_ITEMS];
-    NKey kr[P1_ITEMS];
-#pragma unroll
-    for (int i = 0; i < P1_ITEMS; ++i) {
-        uint8_t c = 0;
-        if (live[i]) {
-            const int fl = flag[i];
-            const bool mapped = !(fl & 0x4), matemapped = !(fl & 0x8), rev = fl & 0x10, materev = fl & 0x20, first = fl & 0x40, second = fl & 0x80, proper = fl & 0x2;
-            c = pass_bits(fl, aux[i], mapq[i], refid[i], A.min_mapq);
-            if (c & C_P1) {
-                const bool skip = (matemapped && mrefid[i] == refid[i] && mpos[i] > pos[i]) || (matemapped && mrefid[i] == refid[i] && mpos[i] == pos[i] && second);
-                if (!skip) c |= C_P3;
-            }
-            if (matemapped && mrefid[i] != -1) c |= C_HASSTUB;
-            const int nblk = (int)(bo1[i] - bo[i]);
-            bool conc = false;
-            if (mapped && matemapped && mrefid[i] != -1 && refid[i] == mrefid[i] && proper) {
-                if (rev && !materev && pos[i] >= mpos[i] && pos[i] - mpos[i] <= 750000) conc = true;
-                else if (!rev && materev && mpos[i] >= pos[i] && mpos[i] - pos[i] <= 750000) conc = true;
-            }
-            if (conc && nblk > 0) {
-                c |= C_CONC;
-                if ((first || second) && !(aux[i] & SQ_AUX_LOWPHRED)) {  // clipped by more than 15 bases at either read end (first / last block in read-offset order)
-                    const int4 f4 = rev ? qb[i] : qa[i], b4 = rev ? qa[i] : qb[i];
-                    const int f_readpos = (int)((uint32_t)f4.z & 0xffffu), b_readpos = (int)((uint32_t)b4.z & 0xffffu), b_matchread = (int)((uint32_t)b4.z >> 16);
-                    if (f_readpos > 15 || totlen[i] - b_readpos - b_matchread > 15) c |= C_PART;
-                }
-            }
-        }
-        cl[i] = c;
-        NKey k = nkey_empty();
-        k.bits = 1;
-        if (live[i]) {
-            const bool rev = flag[i] & 0x10, stub = !(flag[i] & 0x8) && mrefid[i] != -1;
-            const int4 e0 = rev ? qb[i] : qa[i];  // the first own block in read order
-            k.nown = (int)(bo1[i] - bo[i]); k.bits = ((flag[i] & 0x40) ? 1 : 0) | (rev ? 2 : 0) | (stub ? 4 : 0) | ((int)(c & (C_P1 | C_P2)) << 4);
-            k.rid = refid[i]; k.mrid = mrefid[i]; k.mp = mpos[i]; k.e0x = k.nown > 0 ? e0.x : 0; k.e0y = k.nown > 0 ? e0.y : 0;
-        }
-        kr[i] = k;
-        if (lane == 63) s_key[i * NW + wave] = k;
-    }
-    __syncthreads();
-    if (A.ablate == 2) {
-#pragma unroll
-        for (int i = 0; i < P1_ITEMS; ++i) if (live[i]) A.cls[tbase + i * P1_THREADS + tid] = (uint8_t)(cl[i] ^ kr[i].e0x ^ t_K ^ t_dc);
-        return;
-    }
-    int cnt_in[P1_ITEMS];                 // kept records of this (item, wave) in front of the lane
-    unsigned long long ob_in[P1_ITEMS];   // running pair in front of the record inside its (item, wave) (payload: key + 1, 0 = none)
-    bool unsorted = false, negend = false;
-#pragma unroll
-    for (int i = 0; i < P1_ITEMS; ++i) {
-        const int64_t r = tbase + i * P1_THREADS + tid;
-        const uint8_t c = cl[i];
-        // ---- consecutive-duplicate drop.  The record a passing record is compared with is the previous one that passes the same
-        // filter: nearly always the neighbour, whose key sits one lane below
-        const NKey& kq0 = kr[i];
-        NKey km;
-        km.nown = dpp_shr1(kq0.nown); km.bits = dpp_shr1(kq0.bits); km.rid = dpp_shr1(kq0.rid); km.mrid = dpp_shr1(kq0.mrid);
-        km.mp = dpp_shr1(kq0.mp); km.e0x = dpp_shr1(kq0.e0x); km.e0y = dpp_shr1(kq0.e0y);  // (lane 0 is replaced below)
-        if (lane == 0) { const int slot = i * NW + wave; if (slot == 0) km = k_front; else km = s_key[slot - 1]; }
-        const uint8_t pm = (uint8_t)(km.bits >> 4);
-        uint8_t k = 0;
-        if (c & (C_P1 | C_P2)) {
-            bool eq1 = true, eq2 = true;  // Equal to the last record that passed filter 1 / filter 2
-            if (A.ablate == 6) { eq1 = eq2 = (kq0.e0x == km.e0x); }  // (timing only: the duplicate drop without its walks)
-            else if (A.ablate == 9) { const int e = equal_fast(km, kq0); eq1 = eq2 = e != 0; }  // (timing only: no walk, no general case)
-            else if ((c & C_P1) && (c & C_P2) && r > 0 && (pm & C_P1) && (pm & C_P2)) {
-                // the neighbour passed both filters: one comparison answers both questions
-                const int e = equal_fast(km, kq0);
-                eq1 = e == 2 ? key_equal_full(R, r - 1, r) : e == 1;
-                eq2 = eq1;
-            } else dedup_general(R, r, c, km, kq0, A.prior_mask, A.min_mapq, eq1, eq2);
-            if ((c & C_P1) && !eq1) k |= K_1;
-            if (c & C_P2) {
-                const bool eq = eq2;
-                if (!eq) {
-                    k |= K_2;
-                    // whetherbuildedge (SegmentGraph.cpp:1601-1605) on the stub-augmented, sorted record: the stub side always has
-                    // ReadPos 0 <= 15; the own side is tested with its own low-Phred flag
-                    bool build = kq0.nown == 0 || !(kq0.bits & 4);
-                    if (!build) { const int4 e0 = (flag[i] & 0x10) ? qb[i] : qa[i]; build = (int)((uint32_t)e0.z & 0xffffu) <= 15 || (aux[i] & SQ_AUX_LOWPHRED); }
-                    if (build) k |= K_BUILD;
-                }
-            }
-        }
-        if (c & C_P3) k |= K_P3;
-        kp[i] = k;
-        if (live[i] && A.ablate != 10) { A.cls[r] = c; A.keep[r] = k; }
-        // ---- along the kept stream inside this (item, wave): rank, running (otherChr, otherrightmost) pair (SegmentGraph.cpp:655-667; a
-        // max-scan on a sorted stream), order of the kept records (the stream must be coordinate sorted: README.md:23)
-        const bool kept = k & K_1;
-        const unsigned long long km64 = __ballot(kept);
-        cnt_in[i] = (int)__popcll(km64 & ltmask);
-        unsigned long long pay = 0;
-        if (kept && (c & C_CONC) && (flag[i] & 0xC0)) {
-            const int end = qa[i].x + qa[i].y;
-            if (end < 0 || refid[i] < 0) negend = true;
-            pay = (((unsigned long long)(uint32_t)refid[i] << 32) | (uint32_t)end) + 1;
-        }
-        unsigned long long wob;
-        if (A.ablate == 7) { wob = pay; ob_in[i] = pay; }  // (timing only: without the running-pair scan)
-        else ob_in[i] = wave_maxscan_excl_u64(pay, wob);
-        const long long sk = sort_key(refid[i], pos[i]);
-        if (A.ablate == 8) { if (lane == 0) { s_first[i * NW + wave] = sk; s_last[i * NW + wave] = sk; } }  // (timing only: without the order check)
-        else if (km64) {
-            const unsigned long long below = km64 & ltmask;
-            const long long skp = __shfl(sk, below ? 63 - __clzll((long long)below) : 0, 64);
-            if (kept && below && sk < skp) unsorted = true;
-            const int fl_ = __ffsll((long long)km64) - 1, ll_ = 63 - __clzll((long long)km64);  // (uniform: scalar reads)
-            const long long fk = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(sk >> 32), fl_) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)sk, fl_));
-            const long long lk = (long long)(((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(sk >> 32), ll_) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)sk, ll_));
-            if (lane == 0) { s_first[i * NW + wave] = fk; s_last[i * NW + wave] = lk; }
-        } else if (lane == 0) { s_first[i * NW + wave] = LLONG_MIN; s_last[i * NW + wave] = LLONG_MIN; }
-        if (lane == 0) { s_cnt[i * NW + wave] = (int)__popcll(km64); s_ob[i * NW + wave] = wob; }
-    }
-    if (PROF) tp[2] = __builtin_amdgcn_s_memtime();
-    if (A.ablate == 3) return;
-    __syncthreads();
-    // ---- the (item, wave) slots in stream order
-    int e_cnt[P1_ITEMS];
-    unsigned long long e_ob[P1_ITEMS];
-    int tile_cnt = 0;
-    unsigned long long tile_ob = 0;
-    long long tile_sk = LLONG_MIN, tile_first = LLONG_MIN;
-    {
-        int run = 0;
-        unsigned long long runo = 0;
-        long long lastk = LLONG_MIN;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-#pragma unroll
-            for (int i = 0; i < P1_ITEMS; ++i) if (s == i * NW + wave) { e_cnt[i] = run; e_ob[i] = runo; }  // (s is a compile-time constant after unrolling; wave is not)
-            run += s_cnt[s];
-            const unsigned long long o = s_ob[s];
-            runo = o > runo ? o : runo;
-            const long long f = s_first[s];
-            if (f != LLONG_MIN) {
-                if (tile_first == LLONG_MIN) tile_first = f;
-                if (f < lastk) unsorted = true;
-                const long long l = s_last[s];
-                lastk = l > lastk ? l : lastk;
-            }
-        }
-        tile_cnt = run; tile_ob = runo; tile_sk = lastk;
-    }
-    if (tid == 0) { A.tile_first[tile] = tile_first; A.tile_max[tile] = tile_sk; A.tile_cnt[tile] = tile_cnt; A.tile_ob[tile] = tile_ob; }
-    if (A.ablate == 4) return;
-    if (PROF) tp[3] = __builtin_amdgcn_s_memtime();
-    bool z[P1_ITEMS], uni_item[P1_ITEMS];
-    int Kc[P1_ITEMS];
-    int zc_in[P1_ITEMS];  // candidates of this (item, wave) in front of the lane
-#pragma unroll
-    for (int i = 0; i < P1_ITEMS; ++i) {
-        z[i] = false; Kc[i] = 0; uni_item[i] = false;
-        const bool kept = kp[i] & K_1;
-        if (kept) {
-            int K = t_K, dc = t_dc, dr = t_dr, uc = t_uc, us = t_us;
-            bool uni = true;  // the tile's cluster neighbourhood applies to this record
-            if (have_cl) {
-                const long long sk = sort_key(refid[i], pos[i]);
-                if (!(t_uni && sk >= t_key0 && sk <= t_key1)) {
-                    uni = false;
-                    if (refid[i] < 0 || refid[i] >= C.n_ref) negend = true;
-                    else {
-                        K = clusters_passed_idx(C, refid[i], pos[i]);
-                        dc = K > 0 ? C.chr[K - 1] : 0; dr = K > 0 ? C.right[K - 1] : 0;
-                        uc = K < C.n ? C.chr[K] : 0; us = K < C.n ? C.start[K] : 0;
-                    }
-                }
-            }
-            Kc[i] = K;
-            // zero coverage (SegmentGraph.cpp:616-620) with the running pair of this tile alone.  The test can only turn false when
-            // the pair grows, so what passes here is a superset of the zero-coverage records; k_zfinal repeats it with the pair in
-            // front of the tile
-            z[i] = zero_coverage(C, K, true, dc, dr, uc, us, e_ob[i] > ob_in[i] ? e_ob[i] : ob_in[i], LLONG_MIN, refid[i], pos[i], A.RL);
-            // ConcordRest candidates (SegmentGraph.cpp:690-699 pushes, :387-389 pops): the non-first blocks of a concordant record that
-            // can still span a break candidate of the first cluster whose right end lies beyond them
-            if ((cl[i] & C_CONC) && (flag[i] & 0xC0) && K < C.n && bo1[i] - bo[i] > 1) {
-                // (cluster K is the first one not passed by the record: on another chromosome => nothing on this one lies ahead)
-                const int k_chr = uni ? t_uc : uc, k_start = uni ? t_us : us, k_right = uni ? t_ur : C.right[K];
-                const int nblk = (int)(bo1[i] - bo[i]);
-                if (k_chr == refid[i]) {
-                    for (int b = 1; b < nblk; ++b) {
-                        const int4 q = b == nblk - 1 ? qb[i] : R.b_pack[bo[i] + (uint32_t)b];
-                        const int p = q.x;
-                        // first cluster on this chromosome whose right end lies beyond p: cluster K unless the block starts behind it
-                        int lo = K, l_chr = k_chr, l_start = k_start;
-                        if (k_right <= p) {
-                            int hi = C.n;
-                            ++lo;
-                            while (lo < hi) { const int mid = (lo + hi) >> 1; if (C.chr[mid] < refid[i] || (C.chr[mid] == refid[i] && C.right[mid] <= p)) lo = mid + 1; else hi = mid; }
-                            if (lo < C.n) { l_chr = C.chr[lo]; l_start = C.start[lo]; }
-                        }
-                        if (lo < C.n && l_chr == refid[i] && p >= l_start - A.RL) {
-                            const int s = atomicAdd(&A.sc[P1S_REST], 1);
-                            if (s < A.rc_cap) { A.rc_cluster[s] = lo; A.rc_pos[s] = p; A.rc_len[s] = q.y; }
-                        }
-                    }
-                }
-            }
-            uni_item[i] = uni;
-        }
-        // trigger of cluster K - 1 (SegmentGraph.cpp:353): the first kept record with K clusters behind it.  Only a record whose K
-        // differs from its kept predecessor's can be one (inside the wave: the kept lane below; the tile's first kept record
-        // always tries); the plain load keeps all but the first arrival away from the atomic
-        const unsigned long long km64 = __ballot(kept);
-        const unsigned long long below = km64 & ltmask;
-        const int Kp = __shfl(Kc[i], below ? 63 - __clzll((long long)below) : 0, 64);
-        if (kept && Kc[i] > 0) {
-            const int rank = e_cnt[i] + cnt_in[i];
-            // (the first kept record of 64 cannot see its predecessor: it asks, unless the whole tile has passed the same clusters
-            // and it is not the tile's first kept record)
-            const bool tryit = below ? Kc[i] != Kp : (!uni_item[i] || rank == 0);
-            const int v = (tile << P1_VSHIFT) | rank;
-            if (tryit && A.trig[Kc[i] - 1] > v) atomicMin(&A.trig[Kc[i] - 1], v);
-        }
-        const unsigned long long zm = __ballot(z[i]);
-        zc_in[i] = (int)__popcll(zm & ltmask);
-        if (lane == 0) s_zcnt[i * NW + wave] = (int)__popcll(zm);
-    }
-    if (unsorted) atomicOr(&A.sc[P1S_FLAGS], P1F_UNSORTED);
-    if (negend) atomicOr(&A.sc[P1S_FLAGS], P1F_NEGATIVE_END);
-    if (PROF) tp[4] = __builtin_amdgcn_s_memtime();
-    if (A.ablate == 5) return;
-    // ---- the candidates of the tile take one run of slots (a tile with at most P1_ZFIX of them uses its own fixed slots: no round
-    // trip to a counter; the others queue behind those)
-    __syncthreads();
-    int ez[P1_ITEMS];
-    int tile_z = 0;
-    {
-        int run = 0;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-#pragma unroll
-            for (int i = 0; i < P1_ITEMS; ++i) if (s == i * NW + wave) ez[i] = run;
-            run += s_zcnt[s];
-        }
-        tile_z = run;
-    }
-    const bool zfixed = tile_z <= P1_ZFIX;
-    if (tid == 0) {
-        int base = tile * P1_ZFIX;
-        if (!zfixed) base = A.zfix_end + atomicAdd(&A.sc[P1S_ZC], tile_z);
-        A.tile_zbase[tile] = base; A.tile_zcnt[tile] = tile_z;
-        s_zbase = base;
-    }
-    if (PROF) tp[5] = __builtin_amdgcn_s_memtime();
-    if (tile_z) {  // (uniform over the workgroup)
-        if (!zfixed) __syncthreads();
-        const int zb = zfixed ? tile * P1_ZFIX : s_zbase;
-#pragma unroll
-        for (int i = 0; i < P1_ITEMS; ++i) {
-            if (!z[i]) continue;
-            const int slot = zb + ez[i] + zc_in[i];
-            if (slot < A.zcap) {
-                A.zc_v[slot] = (tile << P1_VSHIFT) | (e_cnt[i] + cnt_in[i]); A.zc_K[slot] = Kc[i]; A.zc_ob[slot] = e_ob[i] > ob_in[i] ? e_ob[i] : ob_in[i];
-                A.zc_refid[slot] = refid[i]; A.zc_pos[slot] = pos[i];
-            }
-        }
-    }
-    if (PROF && tid == 0) {
-        tp[6] = tp[7] = __builtin_amdgcn_s_memtime();
-        for (int q = 0; q < 7; ++q) atomicAdd(&prof[q], tp[q + 1] - tp[q]);
-        atomicAdd(&prof[7], 1ull);
-    }
-}
-#else
 // ------------------------------------------------------------------------------------------------ pass 1, one wave per tile
-// Round 5.  The four-wave form above issues 1291 vector + 960 scalar instructions per wave of 128 records (SQ counters, round 4): with
+// Round 5.  The four-wave form of rounds 3/4 (k_pass1, a workgroup per tile of 512 records; removed) issued 1291 vector + 960 scalar instructions per wave of 128 records (SQ counters, round 4): with
 // five waves per SIMD each "issuing" a quarter of its life, the SIMD's issue port is busy all the time -- the kernel is bound by the
 // NUMBER OF INSTRUCTIONS, not by memory (its loads alone run at 5.9 TB/s) and not by latency.  Two thirds of them were control flow and
 // bookkeeping of the workgroup form: 393 exec-mask branches in the code, (item, wave) slots combined through LDS behind two barriers,
@@ -877,7 +517,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
         }
     }
 }
-#endif
 // What runs along the stream, from the per-tile results of k_pass1: kept records and running pair in front of every tile, the
 // totals, the first kept record, the order of neighbouring tiles.  A workgroup scans 1024 tiles (a million records) and first reduces
 // everything in front of them itself -- coalesced reads of a few hundred KB out of L2 -- so no workgroup waits for another.
@@ -1137,10 +776,8 @@ __global__ __launch_bounds__(P1_THREADS) void k_find_rank(int64_t n, const uint8
 // A workgroup of 256 threads takes ST_ITEMS x 256 consecutive records, item i of thread t being record base + i * 256 + t: every
 // load is a coalesced one and a wave works on 64 neighbouring records of the sorted stream (they share their node / breakpoints, so
 // the wave-combined atomics of the bodies below stay cheap).  Stream order = (item, wave, lane).
-#ifndef SQ_ST_THREADS
-#define SQ_ST_THREADS 64   // (round 5: one wave per tile of 256 records -- no barrier waits, k_depth2 0.50 -> 0.43 ms at C3)
-#endif
-constexpr int ST_THREADS = SQ_ST_THREADS, ST_ITEMS = 4, ST_TILE = ST_THREADS * ST_ITEMS, ST_SLOTS = ST_ITEMS * (ST_THREADS / 64);
+// (round 5: one wave per tile of 256 records -- no barrier waits, k_depth2 0.50 -> 0.43 ms at C3)
+constexpr int ST_THREADS = 64, ST_ITEMS = 4, ST_TILE = ST_THREADS * ST_ITEMS, ST_SLOTS = ST_ITEMS * (ST_THREADS / 64);
 // max-scan of non-negative payloads (0 = identity) over the tile in stream order; v[i] in, EXCLUSIVE prefix inside the tile out;
 // returns the tile aggregate.  s_agg: ST_SLOTS words of LDS.
 __device__ __forceinline__ unsigned int st_tile_maxscan(unsigned int (&v)[ST_ITEMS], unsigned int* s_agg) {

@@ -174,7 +174,7 @@ struct Seg {
     size_t ps = 0, pe = 0;
     int disChr = 0, otherChr = 0, nextdisChr = 0, disright = 0, otherright = 0, nextdisright = 0;
     int markStart = -1, markChr = -1;
-    const bool recount = std::getenv("SQUID_REPLAY_CHECK") != nullptr;  // (tests: every candidate counted twice, check_candidate)
+    const bool recount = env_set("SQUID_REPLAY_CHECK");  // (tests: every candidate counted twice, check_candidate)
 
     Seg(const sq_ctx* c, const StreamRec* recs, const SegStatic& st, std::vector<Node>& out)
         : c(c), recs(recs), RL(c->read_len), D(st.D), nd(st.nd), part(st.part), clusters(st.clusters), st(st), out(out) {}
@@ -437,7 +437,7 @@ double segment_clusters(const sq_ctx* c, std::shared_ptr<SegPlan>& plan, std::ve
     plan = std::make_shared<SegPlan>();
     SegStatic& S = plan->st;
     const auto t_begin = std::chrono::steady_clock::now();
-    static const bool laps = std::getenv("SQUID_PREP_DEBUG") != nullptr;
+    static const bool laps = env_set("SQUID_PREP_DEBUG");
     auto lap = [&](const char* what) { if (laps) std::fprintf(stderr, "[clusters] %-22s at %.3f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count()); };
     // ---- discordant blocks and clip positions of the chimeric fragments (SegmentGraph.cpp:203-264)
     S.part.assign(c->ref_len.size(), std::make_pair(0, 0));  // ledger B10
@@ -712,7 +712,7 @@ static int replay_range(sq_ctx* c, SegPlan& plan, size_t a_begin, size_t a_end, 
     if (seed) sink.push_back(*seed);  // the real node in front (the result keeps it, possibly extended)
     else if (virtual_back) sink.push_back(Node{-1, 0, 0, 0, 0.0});
     Seg S(c, plan.compact, plan.st, sink);
-    S.prof = std::getenv("SQUID_REPLAY_PROF") != nullptr;
+    S.prof = env_set("SQUID_REPLAY_PROF");
     SegSupport& sup = plan.sup;
     const std::vector<Blk>& D = S.D;
     const int nd = S.nd, RL = c->read_len;
@@ -722,7 +722,7 @@ static int replay_range(sq_ctx* c, SegPlan& plan, size_t a_begin, size_t a_end, 
     const std::vector<int>& active = plan.active;
     if (nd == 0 || plan.K == 0 || a_begin >= a_end) return SQ_OK;
 
-    static const bool prof = std::getenv("SQUID_REPLAY_PROF") != nullptr;
+    static const bool prof = env_set("SQUID_REPLAY_PROF");
     long long n_pushed = 0, n_clusters = 0;
     double t_cluster = 0;
     auto push_step = [&](int64_t i) {  // SegmentGraph.cpp:649-700 (ConcordRest pushes are covered by rest_by_cluster)
@@ -843,7 +843,7 @@ int segment_replay(sq_ctx* c, SegPlan& plan, std::vector<Node>& seeds, bool virt
     };
     if (na == 0) { if (seed) seeds.assign(1, *seed); return SQ_OK; }
     if (seed) return sequential();  // (rare repair path of a sharded run)
-    static const bool serial_only = std::getenv("SQUID_REPLAY_SERIAL") != nullptr;
+    static const bool serial_only = env_set("SQUID_REPLAY_SERIAL");
     // group boundaries: the stretch opens with a zero-coverage record on a later chromosome than the last record of the
     // stretch before (which is then that record itself or an earlier one)
     const std::vector<int32_t>& Z = plan.sup.zidx;
