@@ -8,6 +8,11 @@
 // where a mate crosses an exon junction, 5 % soft clips > 15 bp, planted junctions at exon
 // boundaries supported by split-read triplets and discordant pairs.
 //
+// Shape knobs (--read-len, --insert, --clip-frac, --clip-len, --multi-frac, --dup-frac, --lowq-frac, --pcrcopy-frac, --polya-frac,
+// --odd-pair-frac, --split-anchor, --contigs) vary what the layout above keeps fixed.  Every draw a knob needs comes from a second
+// stream (`krng`), and only when the knob is given: without knobs the files are byte for byte what they were before the knobs existed
+// (pinned by tests/golden/synth_default_sha256.json).
+//
 // This file is input tooling: it is NOT part of the product data path and not part of oracle/.
 
 #include <zlib.h>
@@ -213,6 +218,54 @@ Rec make_record(Rng& rng, const std::string& name, int refid, int pos, int mapq,
     return r;
 }
 
+// --polya-frac: the stored bases of ONE whole alignment block (M/=/X/I/D run up to the next S/H/N, the unit ReadRec.cpp:52-77 counts A and T
+// over) become all A or all T.  Works on the finished record, so the main random stream never sees it.
+bool polya_block(Rec& r, Rng& krng) {
+    std::vector<uint8_t>& b = r.bytes;
+    uint16_t ncig;
+    std::memcpy(&ncig, b.data() + 16, 2);
+    int32_t lseq;
+    std::memcpy(&lseq, b.data() + 20, 4);
+    const size_t cg = 36 + b[12], sq = cg + 4 * (size_t)ncig;
+    std::vector<std::pair<int, int>> blocks;  // [first stored base, behind the last)
+    int at = 0;
+    for (int k = 0; k < ncig;) {
+        uint32_t v;
+        std::memcpy(&v, b.data() + cg + 4 * k, 4);
+        const int op = v & 15, len = (int)(v >> 4);
+        if (op == 0 || op == 7) {
+            int n = 0;
+            for (; k < ncig; ++k) {
+                std::memcpy(&v, b.data() + cg + 4 * k, 4);
+                const int o = v & 15;
+                if (o == 3 || o == 4 || o == 5) break;
+                if (o != 2) n += (int)(v >> 4);
+            }
+            blocks.push_back({at, at + n});
+            at += n;
+        } else {
+            if (op == 4 || op == 1 || op == 8) at += len;
+            ++k;
+        }
+    }
+    if (blocks.empty() || at > lseq) return false;
+    const std::pair<int, int> blk = blocks[(size_t)(krng.next() % blocks.size())];
+    const uint8_t code = (krng.next() & 1) ? 1 : 8;  // A or T
+    for (int i = blk.first; i < blk.second; ++i) {
+        uint8_t& x = b[sq + (size_t)i / 2];
+        x = (i & 1) ? (uint8_t)((x & 0xf0) | code) : (uint8_t)((x & 0x0f) | (code << 4));
+    }
+    return true;
+}
+
+// "A,B" -> (A, B); "A" -> (A, A)
+template <class T>
+std::pair<T, T> parse_pair(const std::string& v) {
+    const size_t k = v.find(',');
+    const T a = (T)std::atof(v.c_str());
+    return {a, k == std::string::npos ? a : (T)std::atof(v.c_str() + k + 1)};
+}
+
 // ---------------------------------------------------------------- genome model
 struct Gene {
     int chr;
@@ -279,6 +332,16 @@ int main(int argc, char** argv) {
     int n_interleave = 0;          // --interleave K: K PAIRS of junctions that FilterbyInterleaving removes (see the planting loop)
     bool small_cc = false;  // config C5: compact genes, junctions in the last exon (see below)
     double indel_frac = 0.0;  // fraction of concordant pairs whose left read gets an I / D / =X CIGAR variant (off by default: C1..C5 unchanged)
+    // shape knobs; a negative fraction / an unset flag = "not given": the generator then takes the route (and the draws) it always took
+    int RL = 100;                                // --read-len
+    double ins_mean = 300, ins_sd = 30;          // --insert MEAN,SD
+    double clip_frac = -1;                       // --clip-frac (not given: 1 pair in 20, through `dice`)
+    int clip_lo = 16, clip_hi = 30;              // --clip-len LO,HI
+    bool clip_len_set = false;
+    double multi_frac = -1, dup_frac = -1, lowq_frac = -1, pcrcopy_frac = -1;  // not given: 1/211, 1/997, 1/101, 1/61 through `dice`
+    double polya_frac = 0, odd_frac = 0;         // --polya-frac, --odd-pair-frac
+    int anchor_lo = 25, anchor_hi = 75;          // --split-anchor LO,HI
+    std::string contigs_arg;                     // --contigs "LEN,LEN,..." (config T2)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&]() { return std::string(i + 1 < argc ? argv[++i] : ""); };
@@ -295,6 +358,18 @@ int main(int argc, char** argv) {
         else if (a == "--indel-frac") indel_frac = std::atof(val().c_str());
         else if (a == "--bwa") g_bwa = true;
         else if (a == "--interleave") n_interleave = std::atoi(val().c_str());
+        else if (a == "--read-len") RL = std::atoi(val().c_str());
+        else if (a == "--insert") { const auto p = parse_pair<double>(val()); ins_mean = p.first; ins_sd = p.second; }
+        else if (a == "--clip-frac") clip_frac = std::atof(val().c_str());
+        else if (a == "--clip-len") { const auto p = parse_pair<int>(val()); clip_lo = p.first; clip_hi = p.second; clip_len_set = true; }
+        else if (a == "--multi-frac") multi_frac = std::atof(val().c_str());
+        else if (a == "--dup-frac") dup_frac = std::atof(val().c_str());
+        else if (a == "--lowq-frac") lowq_frac = std::atof(val().c_str());
+        else if (a == "--pcrcopy-frac") pcrcopy_frac = std::atof(val().c_str());
+        else if (a == "--polya-frac") polya_frac = std::atof(val().c_str());
+        else if (a == "--odd-pair-frac") odd_frac = std::atof(val().c_str());
+        else if (a == "--split-anchor") { const auto p = parse_pair<int>(val()); anchor_lo = p.first; anchor_hi = p.second; }
+        else if (a == "--contigs") contigs_arg = val();
         else { std::fprintf(stderr, "unknown arg %s\n", a.c_str()); return 2; }
     }
     std::vector<Contig> contigs;
@@ -317,11 +392,30 @@ int main(int argc, char** argv) {
         if (ntsv < 0) ntsv = config == "C5" ? (giant ? 100000 : 110000) : 200;
     } else if (config == "T2") {  // two small contigs: inter-chromosomal test case
         contigs = {{"chrA", 3000000}, {"chrB", 2000000}, {"chrC", 50000}};
+        if (!contigs_arg.empty()) {  // chrA, chrB, ... of the given lengths; a contig shorter than two gene islands receives no gene
+            contigs.clear();
+            for (size_t at = 0; at < contigs_arg.size();) {
+                const size_t k = std::min(contigs_arg.find(',', at), contigs_arg.size());
+                contigs.push_back({std::string("chr") + (char)('A' + contigs.size()), std::atoi(contigs_arg.substr(at, k - at).c_str())});
+                at = k + 1;
+            }
+            if (contigs.empty() || contigs.size() > 26) { std::fprintf(stderr, "--contigs: 1..26 lengths\n"); return 2; }
+            for (auto& c : contigs) if (c.len < 1000) { std::fprintf(stderr, "--contigs: a length below 1000\n"); return 2; }
+        }
         if (records < 0) records = 30000; if (ntsv < 0) ntsv = 8; cfgno = 7;
     } else { std::fprintf(stderr, "unknown config\n"); return 2; }
     if (!seed) seed = 20180000ull + cfgno;
     Rng rng(seed);
-    const int RL = 100;
+    Rng krng(seed ^ 0x5A4B4E4F42ull);  // every draw of a shape knob; untouched when no knob is given
+    if (RL < 40 || RL > 1000 || ins_sd < 0 || clip_lo < 1 || clip_hi < clip_lo || anchor_lo < 1 || anchor_hi < anchor_lo) { std::fprintf(stderr, "bad shape knob\n"); return 2; }
+    if (!contigs_arg.empty() && config != "T2") { std::fprintf(stderr, "--contigs needs --config T2\n"); return 2; }
+    // a split read keeps at least 20 bases on either side (the floor a piece has anyway); 25..75 of 100 bases is inside that
+    anchor_hi = std::min(anchor_hi, RL - 20);
+    anchor_lo = std::min(anchor_lo, anchor_hi);
+    long n_short_clips = 0, n_long_clips = 0, n_polya = 0, n_overlap = 0, n_multi = 0, n_dup = 0, n_lowq = 0, n_pcrcopy = 0;
+    enum { ODD_UNPROPER, ODD_SAME_STRAND, ODD_NEAR_GENE, ODD_FAR, ODD_OTHER_CHR, ODD_MATE_UNMAPPED, ODD_SAME_POS, ODD_KINDS };
+    static const char* const odd_names[ODD_KINDS] = {"odd_unproper", "odd_same_strand", "odd_near_gene", "odd_far", "odd_other_chr", "odd_mate_unmapped", "odd_same_pos"};
+    long n_odd[ODD_KINDS] = {0, 0, 0, 0, 0, 0, 0}, odd_turn = 0;
 
     // ---- genes: roughly one per 'records/1500', at least 3x the junction count
     long total_len = 0;
@@ -436,12 +530,12 @@ int main(int argc, char** argv) {
         int availy = v.yhead ? gy.tlen() - v.txy : v.txy;
         for (int f = 0; f < v.nsplit + v.npair; ++f) {
             bool split = f < v.nsplit;
-            int L = (int)std::lround(300 + 30 * rng.normal());
+            int L = (int)std::lround(ins_mean + ins_sd * rng.normal());
             L = std::max(L, 2 * RL + 10);
             // fragment covers F offsets [s, s+L) relative to the junction at 0
             int s;
             if (split) {
-                int a = rng.range(25, 75);  // bases of the split mate on its first side
+                int a = rng.range(anchor_lo, anchor_hi);  // bases of the split mate on its first side
                 bool m1split = rng.next() & 1;
                 s = m1split ? -a : -(L - RL) - a;  // the junction falls inside mate1 or inside mate2
             } else {
@@ -489,6 +583,7 @@ int main(int argc, char** argv) {
                     int flag = 0x1 | (reverse ? 0x10 : 0) | (m.first ? 0x40 : 0x80);
                     if (npieces == 2 && si == 1) flag |= 0x100;
                     recs.push_back(make_record(rng, name, g.chr, p.refpos, 255, flag, cg, -1, -1, 0, 1, false));
+                    if (polya_frac > 0 && krng.uni() < polya_frac && polya_block(recs.back(), krng)) ++n_polya;
                     rec_mate.push_back((int)(&m - mates));
                     rec_primary.push_back(1);
                     for (size_t q = 0; q + 1 < recs.size(); ++q) if (rec_mate[q] == rec_mate.back()) rec_primary.back() = 0;
@@ -537,15 +632,15 @@ int main(int argc, char** argv) {
     // a few non-chimeric "partial" fragments in the chimeric file (clip positions -> PartAlignPos path)
     for (size_t gi = 0; gi < genes.size() && gi < 40; gi += 3) {
         const Gene& g = genes[gi];
-        if (g.tlen() < 400) continue;
-        int t0 = rng.range(0, g.tlen() - 320);
+        if (g.tlen() < 4 * RL) continue;
+        int t0 = rng.range(0, g.tlen() - 3 * RL - 20);
         std::string name = "part" + std::to_string(gi);
         Piece p1 = map_interval(g, t0 + 20, t0 + RL);
         std::vector<CigarOp> c1 = {{'S', 20}};
         c1.insert(c1.end(), p1.cig.begin(), p1.cig.end());
-        Piece p2 = map_interval(g, t0 + 200, t0 + 300);
-        Rec ra = make_record(rng, name, g.chr, p1.refpos, 255, 0x1 | 0x2 | 0x20 | 0x40, c1, g.chr, p2.refpos, 300, 1, false);
-        Rec rb = make_record(rng, name, g.chr, p2.refpos, 255, 0x1 | 0x2 | 0x10 | 0x80, p2.cig, g.chr, p1.refpos, -300, 1, false);
+        Piece p2 = map_interval(g, t0 + 2 * RL, t0 + 3 * RL);
+        Rec ra = make_record(rng, name, g.chr, p1.refpos, 255, 0x1 | 0x2 | 0x20 | 0x40, c1, g.chr, p2.refpos, 3 * RL, 1, false);
+        Rec rb = make_record(rng, name, g.chr, p2.refpos, 255, 0x1 | 0x2 | 0x10 | 0x80, p2.cig, g.chr, p1.refpos, -3 * RL, 1, false);
         if (g_bwa) { gene_extra[gi].push_back(ra); gene_extra[gi].push_back(rb); continue; }
         chim.push_back(ra);
         chim.push_back(rb);
@@ -587,20 +682,44 @@ int main(int argc, char** argv) {
         recs.clear();
         int T = g.tlen();
         for (long f = 0; f < nf; ++f) {
-            int L = (int)std::lround(300 + 30 * rng.normal());
+            int L = (int)std::lround(ins_mean + ins_sd * rng.normal());
             L = std::min(std::max(L, RL), T);
             int s = rng.range(0, T - L);
             bool m1left = rng.next() & 1;
             std::string name = "r" + std::to_string(frag_id++);
             uint64_t dice = rng.next();
-            bool dup = (dice % 997) == 0;          // flagged PCR duplicate (dropped by every filter)
-            bool multi = ((dice >> 10) % 211) == 0; // multi-mapper: NH 3, MAPQ 3
-            bool lowq = ((dice >> 20) % 101) == 0;
-            bool pcrcopy = ((dice >> 30) % 61) == 0; // identical un-flagged copy of the fragment
+            // (a fraction given on the command line replaces the modulus of `dice` and draws from the knob stream)
+            bool dup = dup_frac < 0 ? (dice % 997) == 0 : krng.uni() < dup_frac;                      // flagged PCR duplicate (dropped by every filter)
+            bool multi = multi_frac < 0 ? ((dice >> 10) % 211) == 0 : krng.uni() < multi_frac;        // multi-mapper: NH 3, MAPQ 3
+            bool lowq = lowq_frac < 0 ? ((dice >> 20) % 101) == 0 : krng.uni() < lowq_frac;
+            bool pcrcopy = pcrcopy_frac < 0 ? ((dice >> 30) % 61) == 0 : krng.uni() < pcrcopy_frac;   // identical un-flagged copy of the fragment
             int clipside = -1, cliplen = 0;
-            if (((dice >> 40) % 20) == 0) { clipside = (int)((dice >> 50) & 3); cliplen = 16 + (int)((dice >> 52) % 15); }
+            if (clip_frac < 0 ? ((dice >> 40) % 20) == 0 : krng.uni() < clip_frac) {
+                clipside = (int)((dice >> 50) & 3);
+                cliplen = clip_len_set ? std::min(krng.range(clip_lo, clip_hi), RL - 20) : 16 + (int)((dice >> 52) % 15);
+            }
+            // --odd-pair-frac: the kinds take turns; one that this fragment cannot have (no later gene where it needs one) leaves a plain pair
+            int odd = -1;
+            size_t g2i = gi;  // gene island the right-hand record lies in
+            if (odd_frac > 0 && krng.uni() < odd_frac) {
+                odd = (int)(odd_turn++ % ODD_KINDS);
+                if (odd == ODD_NEAR_GENE || odd == ODD_FAR || odd == ODD_OTHER_CHR) {
+                    std::vector<size_t> cand;
+                    for (size_t j = gi + 1; j < genes.size(); ++j) {
+                        const long gap = (long)genes[j].es.front() - g.ee.back();
+                        if (odd == ODD_OTHER_CHR ? genes[j].chr != g.chr
+                                                 : genes[j].chr == g.chr && (odd == ODD_NEAR_GENE ? gap + 100000 < 750000 : gap > 750000))
+                            cand.push_back(j);
+                    }
+                    if (cand.empty()) odd = -1;
+                    else g2i = cand[(size_t)(krng.next() % cand.size())];
+                }
+                if (odd == ODD_SAME_POS) L = RL;  // both mates cover the same RL bases
+            }
+            const Gene& g2 = genes[g2i];
+            const int s2 = g2i == gi ? s + L - RL : krng.range(0, g2.tlen() - RL);  // transcript start of the right-hand read
             Piece pl = map_interval(g, s, s + RL);
-            Piece pr = map_interval(g, s + L - RL, s + L);
+            Piece pr = map_interval(g2, s2, s2 + RL);
             auto clip = [&](Piece& p, bool left, int n, const Gene& gg, int t0, int t1) {
                 // replace n transcript bases at one end of the read with a soft clip
                 Piece q = left ? map_interval(gg, t0 + n, t1) : map_interval(gg, t0, t1 - n);
@@ -610,10 +729,17 @@ int main(int argc, char** argv) {
                 if (!left) c.push_back({'S', n});
                 p.refpos = q.refpos; p.cig = c; p.reflen = q.reflen;
             };
+            // mate unmapped: one read stays, the other is written without an alignment at the same place
+            const int unmapped_side = odd == ODD_MATE_UNMAPPED ? (int)(krng.next() & 1) : -1;  // 0: the left read has no alignment, 1: the right one
+            if (clipside >= 0 && unmapped_side == clipside / 2) clipside = -1;
             if (clipside == 0) clip(pl, true, cliplen, g, s, s + RL);
             if (clipside == 1) clip(pl, false, cliplen, g, s, s + RL);
-            if (clipside == 2) clip(pr, true, cliplen, g, s + L - RL, s + L);
-            if (clipside == 3) clip(pr, false, cliplen, g, s + L - RL, s + L);
+            if (clipside == 2) clip(pr, true, cliplen, g2, s2, s2 + RL);
+            if (clipside == 3) clip(pr, false, cliplen, g2, s2, s2 + RL);
+            if (clipside >= 0) ++(cliplen <= 15 ? n_short_clips : n_long_clips);
+            if (g2i == gi && L < 2 * RL && unmapped_side < 0) ++n_overlap;
+            n_dup += dup; n_multi += multi; n_lowq += lowq; n_pcrcopy += pcrcopy;
+            if (odd >= 0) ++n_odd[odd];
             if (indel_frac > 0 && (double)((dice >> 8) & 0xffff) / 65536.0 < indel_frac) {
                 // CIGAR variants of the same alignment: M a, I 2, M b / M a, D 3, M b / = a, X 1, = b on the first long match
                 for (size_t ci = 0; ci < pl.cig.size(); ++ci) {
@@ -632,11 +758,26 @@ int main(int argc, char** argv) {
             int fr = 0x1 | 0x2 | 0x10 | (m1left ? 0x80 : 0x40) | (dup ? 0x400 : 0);
             int mq = multi ? 3 : 255, nh = multi ? 3 : 1;
             int tl = pr.refpos + pr.reflen - pl.refpos;
+            // what the mate fields of either record say: by default the other record's place
+            int lchr = g.chr, lpos = pl.refpos, rchr = g2.chr, rpos = pr.refpos;
+            if (odd == ODD_UNPROPER || odd == ODD_NEAR_GENE) { fl &= ~0x2; fr &= ~0x2; }  // (far and other-chromosome mates keep the flag: distance / chromosome decide alone)
+            if (odd == ODD_SAME_STRAND) {
+                if (krng.next() & 1) { fl &= ~0x20; fr &= ~0x10; }  // both forward
+                else { fl |= 0x10; fr |= 0x20; }                    // both reverse
+            }
+            if (odd == ODD_OTHER_CHR) tl = 0;
+            if (unmapped_side == 1) { fl = (fl & ~0x20) | 0x8; fr = (fr & ~0x10 & ~0x2) | 0x4; rchr = lchr; rpos = lpos; tl = 0; }
+            if (unmapped_side == 0) { fr = (fr & ~0x20) | 0x8; fl = (fl & ~0x20 & ~0x2) | 0x4 | 0x20; lchr = rchr; lpos = rpos; tl = 0; }
             int copies = pcrcopy ? 2 : 1;
             for (int c = 0; c < copies; ++c) {
                 std::string nm = c ? name + "d" : name;
-                recs.push_back(make_record(rng, nm, g.chr, pl.refpos, mq, fl, pl.cig, g.chr, pr.refpos, tl, nh, lowq));
-                recs.push_back(make_record(rng, nm, g.chr, pr.refpos, mq, fr, pr.cig, g.chr, pl.refpos, -tl, nh, false));
+                if (unmapped_side == 0) recs.push_back(make_record(rng, nm, lchr, lpos, 0, fl, {}, rchr, rpos, 0, 0, false));
+                else recs.push_back(make_record(rng, nm, lchr, lpos, mq, fl, pl.cig, rchr, rpos, tl, nh, lowq));
+                if (polya_frac > 0 && unmapped_side != 0 && krng.uni() < polya_frac && polya_block(recs.back(), krng)) ++n_polya;
+                std::vector<Rec>& dst = g2i == gi ? recs : gene_extra[g2i];
+                if (unmapped_side == 1) dst.push_back(make_record(rng, nm, rchr, rpos, 0, fr, {}, lchr, lpos, 0, 0, false));
+                else dst.push_back(make_record(rng, nm, rchr, rpos, mq, fr, pr.cig, lchr, lpos, -tl, nh, false));
+                if (polya_frac > 0 && unmapped_side != 1 && krng.uni() < polya_frac && polya_block(dst.back(), krng)) ++n_polya;
             }
         }
         for (auto& r : gene_extra[gi]) recs.push_back(r);
@@ -726,7 +867,11 @@ int main(int argc, char** argv) {
         std::fclose(tf);
     }
     (void)nblocks;
-    std::printf("{\"config\":\"%s\",\"seed\":%llu,\"concordant_records\":%ld,\"chimeric_records\":%zu,\"genes\":%zu,\"tsv\":%zu}\n",
+    std::printf("{\"config\":\"%s\",\"seed\":%llu,\"concordant_records\":%ld,\"chimeric_records\":%zu,\"genes\":%zu,\"tsv\":%zu",
                 config.c_str(), (unsigned long long)seed, nrec, chim.size(), genes.size(), tsvs.size());
+    // one count per planted kind (fragments of the concordant file; polya_reads counts records of both files)
+    std::printf(",\"read_len\":%d,\"short_clips\":%ld,\"long_clips\":%ld,\"polya_reads\":%ld,\"overlapping_mates\":%ld", RL, n_short_clips, n_long_clips, n_polya, n_overlap);
+    for (int k = 0; k < ODD_KINDS; ++k) std::printf(",\"%s\":%ld", odd_names[k], n_odd[k]);
+    std::printf(",\"multi\":%ld,\"dup\":%ld,\"lowq\":%ld,\"pcrcopy\":%ld}\n", n_multi, n_dup, n_lowq, n_pcrcopy);
     return 0;
 }

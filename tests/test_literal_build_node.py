@@ -22,6 +22,7 @@ import heapq
 import pytest
 
 import oracle_util as ou
+import shapes
 import test_literal_loops as ll
 
 SENTINEL = {"RefID": 0, "RefPos": 0, "ReadPos": 0, "MatchRef": 0, "MatchRead": 0, "IsReverse": False, "IsFirstRead": False}  # ledger B21
@@ -483,7 +484,7 @@ def _build_node_star_literal(rec, chim, ReadLen, ref_len, min_mapq):
 
 CASES = [("C1", (), ()), ("T2", (), ()), ("C2", (), ()), ("C2", ("--support", "2,6"), ("-w", "1", "-a", "50")), ("C2", ("--interleave", "6"), ())]
 # (a C2 case is a minute of Python loops: the CPU suite keeps three inputs, the GPU suite four, all five are covered; every case passed in both when the test was written)
-CPU_CASES = [CASES[0], CASES[1], CASES[2]]
+CPU_CASES = [CASES[0], CASES[1], CASES[2]] + shapes.LITERAL_CASES
 GPU_CASES = [CASES[0], CASES[1], CASES[3], CASES[4]]
 
 

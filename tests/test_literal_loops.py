@@ -38,6 +38,7 @@ import numpy as np
 import pytest
 
 import oracle_util as ou
+import shapes
 
 
 # ---- a BAM record the way BamTools hands it to ReadRec_t::ReadRec_t (ReadRec.cpp:10-88), from the SAM/BAM specification: the fields the
@@ -753,12 +754,12 @@ def _check(rec, chim, nodes, n_break, kept_total, edges=None):
         assert _build_edges_literal(nodes, copy.deepcopy(chim), rec, 255) == [tuple(e[:5]) for e in edges]
 
 
-@pytest.mark.parametrize("cfg", ["C1", "T2"])
-def test_oracle_against_the_literal_loops(built, synth, tmp_path, cfg):
+@pytest.mark.parametrize("cfg,gen", [("C1", ()), ("T2", ())] + [c[:2] for c in shapes.LITERAL_CASES], ids=["C1", "T2"] + shapes.LITERAL_IDS)
+def test_oracle_against_the_literal_loops(built, synth, tmp_path, cfg, gen):
     """CPU: the oracle's BuildNode_STAR bookkeeping (kept records, the record the loop breaks at) and its per-node Support / AvgDepth
     against the literal loops over records decoded by the literal constructor above -- a reading of the reference that shares no
     code with oracle/"""
-    pre = synth(cfg)
+    pre = synth(cfg, *gen)
     _, dump = ou.run_oracle(built, pre, tmp_path)
     stats = dict(line.split("\t") for line in (dump / "order_stats.txt").read_text().splitlines())
     rec = _records_from_bam(f"{pre}.bam", _chim_names(dump))
@@ -788,12 +789,12 @@ def test_hip_path_against_the_literal_loops(built, synth, tmp_path, cfg, monkeyp
     _check(rec, _read_chimrecord(dump / "chimrecord.txt"), nodes, counts["n_break"], counts["n_kept_p1"], edges)
 
 
-@pytest.mark.parametrize("cfg", ["C1", "T2", "C2"])
-def test_oracle_chimeric_fragments_against_the_literal_build(built, synth, tmp_path, cfg):
+@pytest.mark.parametrize("cfg,gen", [("C1", ()), ("T2", ()), ("C2", ())] + [c[:2] for c in shapes.LITERAL_CASES], ids=["C1", "T2", "C2"] + shapes.LITERAL_IDS)
+def test_oracle_chimeric_fragments_against_the_literal_build(built, synth, tmp_path, cfg, gen):
     """CPU: the merged, sorted, de-duplicated chimeric fragments the oracle dumps (what every other literal loop takes as given) against
     the literal BuildChimericSBamRecord over the chimeric BAM decoded by the literal constructor -- names, lengths, low-Phred flags of the
     sides that have blocks, every block, the order of the fragments, and the read length"""
-    pre = synth(cfg)
+    pre = synth(cfg, *gen)
     _, dump = ou.run_oracle(built, pre, tmp_path)
     want = _read_chimrecord(dump / "chimrecord.txt")
     want_len = int(open(dump / "chimrecord.txt").readline().split("=")[1])
@@ -902,13 +903,13 @@ def _exact_breakpoints_literal(nodes, chim):
     return {e: _count_top(e, x) for e, x in bp.items()}
 
 
-@pytest.mark.parametrize("cfg", ["C1", "T2", "C2"])
-def test_oracle_exact_breakpoints_against_the_literal_loop(built, synth, tmp_path, cfg):
+@pytest.mark.parametrize("cfg,gen", [("C1", ()), ("T2", ()), ("C2", ())] + [c[:2] for c in shapes.LITERAL_CASES], ids=["C1", "T2", "C2"] + shapes.LITERAL_IDS)
+def test_oracle_exact_breakpoints_against_the_literal_loop(built, synth, tmp_path, cfg, gen):
     """CPU: the breakpoint pairs of every edge of the final graph (what `_sv.txt` prints as positions) from the literal ExactBreakpoint +
     CountTop, run over the fragments after the literal RawEdgesChim has trimmed them, against the oracle's breakpoints.txt"""
     import copy
 
-    pre = synth(cfg)
+    pre = synth(cfg, *gen)
     _, dump = ou.run_oracle(built, pre, tmp_path)
     chim = _read_chimrecord(dump / "chimrecord.txt")
     _raw_edges_chim(_Edges([n[:3] for n in ou.read_nodes(dump / "nodes_build.txt")]), chim)  # (trims the blocks in place, as the reference does)
@@ -1035,7 +1036,7 @@ def _filter_edges_literal(nodes, edges, keep, min_w=5, max_deg=5, dist_pos=50000
 
 
 @pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", (), ()), ("T2", (), ("-w", "2")), ("C2", ("--support", "2,6"), ("-w", "1", "-a", "50")),
-                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())])
+                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())] + shapes.LITERAL_CASES)
 def test_oracle_filter_edges_against_the_literal_loop(built, synth, tmp_path, cfg, gen, flags):
     """CPU: the edges that survive FilterEdges (GroupConnection / GroupSelect per node, the depth-ratio rule, the set difference with the
     deleted edges) from the literal loop over the oracle's stage in front of it (nodes with depths, edges with group weights, KeepEdge of
@@ -1156,7 +1157,7 @@ def _filter_by_weight_literal(nodes, edges, min_w=5, dist_pos=50000, dist_idx=20
 
 
 @pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", (), ("-w", "2")), ("C2", ("--support", "2,6"), ("-w", "1", "-a", "50")),
-                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())])
+                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())] + shapes.LITERAL_CASES)
 def test_oracle_filter_by_weight_against_the_literal_loop(built, synth, tmp_path, cfg, gen, flags):
     """CPU: the group weight of every edge and the edges that pass the relaxed threshold, from the literal FilterbyWeight over the oracle's
     BuildEdges stage, against the oracle's stage behind it"""
@@ -1203,7 +1204,7 @@ def _compress_node_literal(nodes, edges):
     return new, [(old_new[e[0]], e[1], old_new[e[2]], e[3]) + tuple(e[4:6]) for e in edges]
 
 
-@pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", (), ()), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())])
+@pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", (), ()), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())] + shapes.LITERAL_CASES)
 def test_oracle_compress_node_against_the_literal_loop(built, synth, tmp_path, cfg, gen, flags):
     """CPU: node table and re-indexed edges behind CompressNode from the literal loop over the oracle's stage in front of it -- the merged
     nodes' AvgDepth as the same IEEE doubles (summed and divided in the reference's order)"""
@@ -1377,7 +1378,7 @@ def _further_compress_literal(nodes, edges, dist_pos=50000, dist_idx=20, ratio=8
 
 
 @pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", (), ()), ("C2", ("--support", "2,6"), ("-w", "1", "-a", "50")),
-                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())])
+                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ())] + shapes.LITERAL_CASES)
 def test_oracle_final_graph_against_the_literal_loops(built, synth, tmp_path, cfg, gen, flags):
     """CPU: the final node table, the component labels and the final edges (weights of discordant edges multiplied) from the literal
     FurtherCompressNode + ConnectedComponent + MultiplyDisEdges over the oracle's stage behind CompressNode, against the oracle's final
@@ -1446,7 +1447,7 @@ def _write_bedpe_literal(refnames, nodes, edges, bps, orders, ratio=8, dist_pos=
 
 
 @pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", (), ()), ("C2", ("--support", "2,6"), ("-w", "1", "-a", "50")),
-                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50"))])
+                                           ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50"))] + shapes.LITERAL_CASES)
 def test_oracle_sv_text_against_the_literal_writer(built, synth, tmp_path, cfg, gen, flags):
     """CPU: `_sv.txt` byte for byte from the literal WriteBEDPE over the oracle's final graph, component orders and breakpoints (row order
     among equal scores included)"""
@@ -1542,7 +1543,7 @@ def _filter_by_interleaving_literal(nodes, edges, dist_pos=50000, dist_idx=20):
 
 @pytest.mark.parametrize("cfg,gen,flags", [("C1", (), ()), ("T2", (), ()), ("C2", ("--support", "2,6"), ("-w", "1", "-a", "50")),
                                            ("C5", ("--records", "300000", "--tsv", "1500"), ("-w", "1", "-a", "50")), ("C5", ("--records", "300000", "--tsv", "1500", "--support", "2,8"), ()),
-                                           ("T2", ("--interleave", "3"), ()), ("C2", ("--interleave", "6"), ()), ("C5", ("--records", "300000", "--tsv", "1500", "--interleave", "40"), ("-w", "1", "-a", "50"))])
+                                           ("T2", ("--interleave", "3"), ()), ("C2", ("--interleave", "6"), ()), ("C5", ("--records", "300000", "--tsv", "1500", "--interleave", "40"), ("-w", "1", "-a", "50"))] + shapes.LITERAL_CASES)
 def test_oracle_filter_by_interleaving_against_the_literal_loop(built, synth, tmp_path, cfg, gen, flags):
     """CPU: KeepEdge of FilterbyInterleaving from the literal loop over the oracle's stage behind FilterbyWeight, against the oracle's.  The
     default generator settings plant no interleaved junction pairs (the answer is "keep" everywhere: those samples pin the walks and the
