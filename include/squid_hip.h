@@ -114,10 +114,10 @@ int sq_ingest_concordant_file(sq_ctx* c, const char* bam_path, int32_t n_threads
  * sq_ingest_chimeric_file followed by sq_ingest_concordant_file; an error of either file is returned. */
 int sq_ingest_files(sq_ctx* c, const char* chim_bam_path, const char* bam_path, int32_t n_threads);
 /* `squid --bwa` (src/Config.cpp:98-100, src/main.cpp:33-37): ONE coordinate-sorted BAM in which split reads are supplementary records
- * and no separate chimeric file exists.  The records are decoded on host threads together with their QNAMEs and stay on the host;
+ * and no separate chimeric file exists.  The records are decoded together with their QNAMEs and kept on the host;
  * sq_build_graph then runs BuildNode_BWA (src/SegmentGraph.cpp:833-1205) and RawEdges (:1698-1930, which also rebuilds the chimeric
  * fragments from the partially aligned reads) over them and continues with the same graph stages as the STAR path; sq_call_sv counts
- * the breakpoint support over the same batch.  sq_params.min_mapqual is the caller's (-mq, default 1: the STAR => 255 rule of
+ * the breakpoint support over the same batch -- on the host threads, or, with sq_bwa_on_device, over a copy of the batch in HBM.  sq_params.min_mapqual is the caller's (-mq, default 1: the STAR => 255 rule of
  * Config.cpp:221-222 does not apply).  A chimeric file ingested before (`-c` next to `--bwa`) only contributes its ReadLen, as in
  * the reference.  Not available to a chromosome-sharded context. */
 int sq_ingest_bwa_file(sq_ctx* c, const char* bam_path, int32_t n_threads);
@@ -170,6 +170,18 @@ int sq_keep_stage_graphs(sq_ctx* c, int32_t on);
  * device route whatever this call says.  A stage with more than 2^20 fragments whose first block has to be resolved in fragment order takes
  * the host route by itself (sq_get_timing: chim_device_fallback counts these, chim_soft_fragments the fragments resolved in order). */
 int sq_chimeric_on_device(sq_ctx* c, int32_t on);
+/* on != 0: a --bwa context (sq_ingest_bwa_file) also keeps its decoded batch in the device record table -- copied there once per ingested batch
+ * by the first sq_build_graph that finds the switch on, next to the seed-node loop, and kept across sq_reset until sq_clear_records, the next
+ * sq_ingest_bwa_file or sq_destroy --, and the two record loops of the mode that are not order-dependent automata run there: the node depth of
+ * BuildNode_BWA (src/SegmentGraph.cpp:1180-1200, the one-way cursor restated as a prefix maximum) and ExactBPConcordantSupport (:3129-3166, on
+ * the breakpoint kernels of the STAR path behind a class byte per record).  BuildNode_BWA's automaton and RawEdges stay on the host threads,
+ * over the host batch.  Every result is identical to the host route's.  Default: off.  Accepted on any context; only a --bwa context looks at
+ * it.  May be switched between sq_reset runs on the same context.  SQUID_BWA_STAGES_GPU=1 / =0 in the environment of sq_create forces /
+ * forbids the route whatever this call says.  An input whose Reads list does not keep its chromosomes in order (an unsorted file), or a record
+ * of more than 256 aligned blocks, takes the host loops for that graph by itself (sq_get_timing: bwa_device_fallback counts these;
+ * bwa_depth_held_blocks: the blocks the cursor holds in front of a later node, ledger W6; bwa_reads_records / bwa_bp_records: the records the
+ * two loops look at, on either route).  sq_save_records refuses a context whose resident table is a --bwa batch. */
+int sq_bwa_on_device(sq_ctx* c, int32_t on);
 
 /* vector<vector<int>> Ordering() -- src/SegmentGraph.cpp:3236-3262: CSR of signed 1-based node ids */
 typedef struct sq_orders {
@@ -297,7 +309,8 @@ int sq_get_counts(sq_ctx* c, sq_counts* k);
 /* tests: copy the HBM-resident record SoA back into a library-owned host batch */
 int sq_debug_download(sq_ctx* c, sq_aln_batch* b);
 /* tests: ExactBPConcordantSupport's counting loop (src/SegmentGraph.cpp:3129-3166) over the resident records for an
- * arbitrary sorted breakpoint list; host_walk != 0 takes the serial host restatement instead of the K10 kernels */
+ * arbitrary sorted breakpoint list; host_walk != 0 takes the serial host restatement instead of the K10 kernels.  A --bwa context whose
+ * graph was built with sq_bwa_on_device answers from its device table, and with host_walk != 0 from the host loop over the same batch */
 int sq_debug_bp_support(sq_ctx* c, int32_t n_bp, const int32_t* chr, const int32_t* pos, int32_t* coverage, int32_t host_walk);
 /* tests: one instance of the per-component ordering problem (GenerateILP, src/SegmentGraph.cpp:3763-3983) on local nodes
  * 0..n-1; edges5 = n_edges x {u, v, head_u, head_v, weight}, u < v.  use_gpu: k_order_small (n <= 8) / k_order_mid (9..19), else
@@ -320,6 +333,12 @@ int sq_debug_blocks(int32_t n, const int32_t* fields7, uint8_t* rel5, int32_t* p
  * table), pairs in the largest hit group}.  Returns SQ_OK when both routes could be run. */
 int sq_debug_chim_stages(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
                          const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8);
+/* tests: the node depth loop of BuildNode_BWA (src/SegmentGraph.cpp:1180-1200) on caller-supplied tables.  nodes3: n_nodes x {chr, pos, len},
+ * sorted, the nodes of a chromosome not overlapping; reads3: n_reads x {RefID, RefPos, MatchRef}, the Reads list in its order.  route 0: the host
+ * loop (needs no device: c may be null); route 1: the kernels of sq_bwa_on_device.  support / sums: per node the count and the 32-bit sum of
+ * MatchRef (AvgDepth = 1.0 * sum / Length); out2 = {blocks the cursor held in front of a later node than their own (route 1), 1 when the
+ * kernels saw a chromosome go down along Reads and returned nothing -- the library then takes the host loop (route 1)}. */
+int sq_debug_bwa_depth(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, int32_t* support, int32_t* sums, int64_t* out2);
 /* tuning: the two BGZF inflate kernels on the first max_blocks blocks of a file, each ALONE on the device, timed with HIP events (the
  * reader overlaps them with everything else).  variant: 2 = the lane-per-block token pass (k_inflate_tok2), else CH * 100 + PB of the
  * wave-per-block pass (k_inflate_spec: 51211, 51210, 25610, 25611, 38411, 102411).  check != 0 compares every block with zlib.

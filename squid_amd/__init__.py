@@ -25,7 +25,7 @@ EXPORTS = [
     "sq_set_shard", "sq_exchange_pack", "sq_exchange_unpack", "sq_get_timing", "sq_timing_accumulate", "sq_reset", "sq_ingest_files", "sq_stage_bam", "sq_clear_records", "sq_set_source", "sq_save_records", "sq_load_records", "sq_get_counts", "sq_debug_download", "sq_debug_bp_support", "sq_debug_order", "sq_debug_blocks", "sq_drop_file_cache",
     "sq_total_order", "sq_set_allgather", "sq_rccl_unique_id", "sq_rccl_init", "sq_rccl_attach", "sq_exchange", "sq_exchange_stats",
     "sq_rccl_available", "sq_rccl_release", "sq_debug_rccl_selftest", "sq_debug_token_bench", "sq_ingest_bwa_file", "sq_junction_sequences", "sq_release_reader_buffers", "sq_keep_host_memory", "sq_keep_stage_graphs",
-    "sq_chimeric_on_device", "sq_debug_chim_stages",
+    "sq_chimeric_on_device", "sq_debug_chim_stages", "sq_bwa_on_device", "sq_debug_bwa_depth",
 ]
 
 
@@ -110,6 +110,8 @@ def load_library() -> C.CDLL:
         lib.sq_keep_stage_graphs.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_chimeric_on_device.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_debug_chim_stages.argtypes = [C.c_void_p, C.c_int32, _P32, C.c_int32, _P32, C.c_int32, _P32, _P32, _P32, _P32, C.c_int32, _P32, C.POINTER(C.c_int64)]
+        lib.sq_bwa_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_debug_bwa_depth.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _P32, C.c_int64, _P32, _P32, _P32, C.POINTER(C.c_int64)]
         lib.sq_clear_records.argtypes = [C.c_void_p]
         lib.sq_release_reader_buffers.argtypes = [C.c_void_p]
         lib.sq_set_source.argtypes = [C.c_void_p, C.c_char_p]
@@ -167,6 +169,21 @@ def read_header(bam_path: str):
     if rc:
         raise SquidError(f"cannot read BAM header of {bam_path}: {lib.sq_strerror(rc).decode()}")
     return names.value.decode().split("\n")[: n.value], list(lens[: n.value])
+
+
+def debug_bwa_depth(nodes, reads, route: int = 0, handle=None) -> dict:
+    """sq_debug_bwa_depth; route 0 (the host loop) needs neither a context nor a device"""
+    import numpy as np
+
+    lib = load_library()
+    nd = np.ascontiguousarray(np.asarray(nodes, dtype=np.int32).reshape(-1, 3))
+    rd = np.ascontiguousarray(np.asarray(reads, dtype=np.int32).reshape(-1, 3))
+    support, sums = np.zeros(max(len(nd), 1), np.int32), np.zeros(max(len(nd), 1), np.int32)
+    out = (C.c_int64 * 2)()
+    rc = lib.sq_debug_bwa_depth(handle, route, len(nd), nd.ctypes.data_as(_P32), len(rd), rd.ctypes.data_as(_P32), support.ctypes.data_as(_P32), sums.ctypes.data_as(_P32), out)
+    if rc:
+        raise SquidError(f"sq_debug_bwa_depth: {lib.sq_strerror(rc).decode()}" + (f" ({lib.sq_last_error(handle).decode()})" if handle else ""))
+    return {"support": support[: len(nd)].tolist(), "sums": sums[: len(nd)].tolist(), "held": int(out[0]), "fallback": int(out[1])}
 
 
 class Context:
@@ -235,6 +252,16 @@ class Context:
         """sq_chimeric_on_device: the next build_graph computes the chimeric raw edges and the per-edge breakpoint lists on the device (same
         results; off by default; a --bwa context ignores it)"""
         self._chk(self.lib.sq_chimeric_on_device(self.h, 1 if on else 0), "sq_chimeric_on_device")
+
+    def bwa_on_device(self, on: bool = True):
+        """sq_bwa_on_device: a --bwa context keeps its batch in HBM as well and the next build_graph / call_sv compute the node depth and the
+        breakpoint support there (same results; off by default; any other context ignores it)"""
+        self._chk(self.lib.sq_bwa_on_device(self.h, 1 if on else 0), "sq_bwa_on_device")
+
+    def debug_bwa_depth(self, nodes, reads, route: int = 1) -> dict:
+        """sq_debug_bwa_depth (tests): the node depth loop of BuildNode_BWA on the given tables, route 0 = the host loop, 1 = the kernels.
+        nodes: [(chr, pos, len)]; reads: [(chr, refpos, matchref)] in Reads order"""
+        return debug_bwa_depth(nodes, reads, route, self.h)
 
     def debug_chim_stages(self, nodes1, nodes2, frags, edges) -> dict:
         """sq_debug_chim_stages (tests): both chimeric graph stages on the given tables by the host and by the device route, compared.  nodes: [(chr,

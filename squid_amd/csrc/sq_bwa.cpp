@@ -9,8 +9,10 @@
 // names kept next to the records on the device and copied back with them, round 5; 0.3-0.6 s for 50.8 M records where sixteen host
 // threads took 3.3-4.5 s), on host threads otherwise --, the two order-dependent loops run on the host over that batch, and the graph from the edge reduction on takes the same kernels as the STAR
 // path (filters, compression, components, ordering).  The breakpoint support (ExactBPConcordantSupport, mode-independent in the
-// reference) is counted on the host, over the same batch.  Not the path BASELINE.json measures; built for drop-in completeness and
-// held to the same parity bar (tests/test_bwa.py).
+// reference) is counted on the host, over the same batch.  With sq_bwa_on_device the batch is also made resident in HBM (DeviceRecords, the
+// layout of the STAR path) and the two loops that are not automata run there: the node depth as a prefix maximum (sq_bwa_stage.inc) and
+// the breakpoint support on the kernels of the STAR path (dev_breakpoint_support), behind a class byte per record.  Not the path
+// BASELINE.json measures; built for drop-in completeness and held to the same parity bar (tests/test_bwa.py, tests/test_bwa_stage_gpu.py).
 //
 // Quirks of the reference reproduced (ledger W1-W6): capacity-driven window compaction, front() for [offset],
 // the last Qname group never flushed, LocateRead hint left over from the BAM loop, weight -1 edges of multi-aligned second mates, the
@@ -109,6 +111,7 @@ struct SeedRun {
     Window conc, dis, part;
     std::vector<Node> seeds;
     std::vector<Blk> reads;
+    int64_t n_reads_records = 0;  // records that fed `reads`
     std::vector<int> margins;
 };
 inline bool seed_record_passes(const HostBatch& hb, size_t ri) {
@@ -134,7 +137,7 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
     if (!opening && ((!dis.none() && r.refid() != dis.head().refid) || (!conc.none() && r.refid() != conc.head().refid) || (!part.none() && r.refid() != part.head().refid))) { other_right = 0; S.oth_set = true; }
     const size_t nb = r.nblk();
     if (nb == 0) return;
-    if (!closing) for (size_t k = 0; k < nb; ++k) S.reads.push_back(r.blk(k));
+    if (!closing) { for (size_t k = 0; k < nb; ++k) S.reads.push_back(r.blk(k)); ++S.n_reads_records; }
     const Blk b0 = r.blk(0), blast = r.blk(nb - 1);
     if (!opening && conc.none() && part.none() && dis.none()) prev0 = r.pos();
     if (!opening && !dis.none() && (dis.v.back().refid != r.refid() || dis_right + RL < r.pos())) {
@@ -246,7 +249,7 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
 // SQUID_BWA_PIECE=<records>: length of a stretch of the parallel --bwa loops (tests: short stretches and a short warm-up on small inputs); 0: by size
 static long bwa_piece_env() { return (long)env_int("SQUID_BWA_PIECE", 0); }
 
-static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& seeds, std::vector<std::vector<Blk>>& reads) {
+static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& seeds, std::vector<std::vector<Blk>>& reads, int64_t& n_reads_records) {
     const size_t nrec = hb.size();
     // ReadLen as the loop leaves it (:857-864): the chimeric file's value, raised by the first five records
     int RL_final = c->read_len;
@@ -354,28 +357,54 @@ static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& see
         }
     }
     reads.clear();
-    for (SeedRun& S : runs) { seeds.insert(seeds.end(), S.seeds.begin(), S.seeds.end()); reads.push_back(std::move(S.reads)); }
+    n_reads_records = 0;
+    for (SeedRun& S : runs) { seeds.insert(seeds.end(), S.seeds.begin(), S.seeds.end()); reads.push_back(std::move(S.reads)); n_reads_records += S.n_reads_records; }
     c->read_len = runs.back().RL;
     return SQ_OK;
 }
 
-// Support / AvgDepth of the tiled nodes (:1180-1204): one pass, the cursor never goes back (W6)
-static void bwa_node_depth(std::vector<Node>& N, const std::vector<std::vector<Blk>>& parts) {
+// Support / AvgDepth of the tiled nodes (:1180-1204): one pass, the cursor never goes back (W6).  The loop proper, into a count and a
+// 32-bit sum per node; false: no read at all
+static bool bwa_node_depth_sums(const std::vector<Node>& N, const std::vector<std::vector<Blk>>& parts, std::vector<int32_t>& cnts, std::vector<int32_t>& sums) {
+    cnts.assign(N.size(), 0); sums.assign(N.size(), 0);
     size_t pi = 0, it = 0;
     auto skip_empty = [&]() { while (pi < parts.size() && it == parts[pi].size()) { ++pi; it = 0; } };
     skip_empty();
-    if (pi == parts.size()) return;  // (no read at all: the reference leaves Support / AvgDepth as constructed)
-    for (Node& n : N) {
-        int cnt = 0, sum = 0;
+    if (pi == parts.size()) return false;
+    for (size_t i = 0; i < N.size(); ++i) {
+        const Node& n = N[i];
+        int cnt = 0;
+        uint32_t sum = 0;  // (the reference's int, with the wrap-around written out)
         for (; pi < parts.size(); ++it, skip_empty()) {
             const Blk& b = parts[pi][it];
-            if (b.refid == n.chr && b.refpos >= n.pos && b.refpos + b.matchref <= n.pos + n.len) { ++cnt; sum += b.matchref; }
+            if (b.refid == n.chr && b.refpos >= n.pos && b.refpos + b.matchref <= n.pos + n.len) { ++cnt; sum += (uint32_t)b.matchref; }
             else if (b.refpos >= n.pos + n.len || b.refid != n.chr) break;
         }
-        n.support = cnt;
-        n.depth = 1.0 * sum / n.len;
+        cnts[i] = cnt; sums[i] = (int32_t)sum;
+    }
+    return true;
+}
+void bwa_set_node_depths(std::vector<Node>& N, const std::vector<int32_t>& cnts, const std::vector<int32_t>& sums) {
+    for (size_t i = 0; i < N.size(); ++i) {
+        Node& n = N[i];
+        n.support = cnts[i];
+        n.depth = 1.0 * sums[i] / n.len;
         n.depth_lo = n.depth_hi = n.depth;
     }
+}
+static void bwa_node_depth(std::vector<Node>& N, const std::vector<std::vector<Blk>>& parts) {
+    std::vector<int32_t> cnts, sums;
+    if (!bwa_node_depth_sums(N, parts, cnts, sums)) return;  // (no read at all: the reference leaves Support / AvgDepth as constructed)
+    bwa_set_node_depths(N, cnts, sums);
+}
+// the same loop on flat tables (sq_debug_bwa_depth route 0, tools/bwa_stage_emu.cpp): nodes3 = {chr, pos, len}, reads3 = {chr, refpos, matchref}
+void bwa_node_depth_flat(int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums) {
+    std::vector<Node> N((size_t)n_nodes);
+    for (int32_t i = 0; i < n_nodes; ++i) N[(size_t)i] = Node{nodes3[3 * i], nodes3[3 * i + 1], nodes3[3 * i + 2], 0, 0.0};
+    std::vector<std::vector<Blk>> parts(1);
+    parts[0].resize((size_t)n_reads);
+    for (int64_t j = 0; j < n_reads; ++j) parts[0][(size_t)j] = Blk{reads3[3 * j], reads3[3 * j + 1], 0, reads3[3 * j + 2], 0, false, false};
+    bwa_node_depth_sums(N, parts, cnts, sums);
 }
 
 static int bwa_home_node(const std::vector<Node>& N, int start, const Blk& b) {  // the two walks of :1757-1758 as binary searches
@@ -608,6 +637,27 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
     return SQ_OK;
 }
 
+// the device route's part of BuildNode_BWA: node table, class bytes (READS) and the depth kernels over the resident table.
+// fallback: the kernels found a chromosome going down along Reads -- nothing was written, the caller takes the host loop
+static int bwa_depth_on_device(sq_ctx* c, bool& fallback, int64_t& n_reads_records) {
+    int rc = dev_upload_nodes(c, c->nodes);
+    if (rc) return rc;
+    int64_t n_p3 = 0, n_reads_blocks = 0;
+    rc = dev_bwa_classify(c, nullptr, n_reads_records, n_p3, n_reads_blocks);
+    if (rc) return rc;
+    c->bwa_p3_ready = false;
+    std::vector<int32_t> cnts, sums;
+    int64_t held = 0;
+    fallback = false;
+    if (n_reads_blocks) {  // (no read at all: the reference leaves Support / AvgDepth as constructed)
+        rc = dev_bwa_node_depth(c, (int)c->nodes.size(), cnts, sums, held, fallback);
+        if (rc) return rc;
+        if (!fallback) bwa_set_node_depths(c->nodes, cnts, sums);
+    }
+    c->timer.add("bwa_depth_held_blocks", 0.0, 0.0, fallback ? 0 : held);
+    return SQ_OK;
+}
+
 // BuildNode_BWA + RawEdges: c->nodes, c->frags and the raw edge list
 int bwa_nodes_and_edges(sq_ctx* c, std::vector<Edge>& raw) {
     if (!c->bwa) return fail(c, SQ_E_ARG, "sq_ingest_bwa_file first");
@@ -615,30 +665,74 @@ int bwa_nodes_and_edges(sq_ctx* c, std::vector<Edge>& raw) {
     std::vector<Node> seeds;
     std::vector<std::vector<Blk>> reads;  // (the Reads list, stretch by stretch)
     int rc;
-    { HostClock hc(c, "host_bwa_seed_nodes"); rc = bwa_seed_nodes(c, hb, seeds, reads); }
+    // sq_bwa_on_device: the batch goes to HBM once, on a thread of its own next to the seed nodes (which need nothing from the device; a
+    // task of the pool that waits for tasks of the pool can starve, segment_clusters) -- joined in front of the depth stage
+    const bool route = c->dev && c->bwa_dev_on();
+    c->bwa_dev_active = false;
+    std::thread upload;
+    int up_rc = SQ_OK;
+    std::string up_err;
+    double up_ms = 0;
+    struct Joiner { std::thread& t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{upload};  // (an exception of the seed nodes must not meet a running thread)
+    if (route && !c->bwa_resident)
+        upload = std::thread([&]() {
+            ErrSink sink(&up_err);
+            const auto t0 = std::chrono::steady_clock::now();
+            up_rc = dev_bwa_upload(c, hb);
+            up_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        });
+    int64_t n_reads_records = 0;
+    { HostClock hc(c, "host_bwa_seed_nodes"); rc = bwa_seed_nodes(c, hb, seeds, reads, n_reads_records); }
+    if (upload.joinable()) {
+        const auto t0 = std::chrono::steady_clock::now();
+        upload.join();
+        c->timer.add("bwa_upload", up_ms, 0.0, 1);
+        c->timer.add("bwa_upload_wait", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 0.0, 1);  // (what did not hide behind the seed nodes)
+        if (up_rc == SQ_OK) c->bwa_resident = true;
+    }
     if (rc) return rc;
+    if (up_rc != SQ_OK && up_rc != SQ_E_CAPACITY) return fail(c, up_rc, up_err);  // (only a batch the table cannot hold goes back to the host loops)
     c->counts.read_len = c->read_len;
     { HostClock hc(c, "host_tile_genome"); rc = tile_genome(c, seeds, c->nodes); }
     if (rc) return rc;
-    { HostClock hc(c, "host_bwa_node_depth"); bwa_node_depth(c->nodes, reads); }
+    bool on_device = false;
+    if (route) {
+        // (a batch the device table cannot hold -- a record of more than 256 blocks -- keeps the host route for this graph)
+        bool fallback = !c->bwa_resident;
+        if (!fallback) {
+            int64_t dev_reads = 0;
+            rc = bwa_depth_on_device(c, fallback, dev_reads);
+            if (rc) return rc;
+            c->bwa_dev_active = true;
+            on_device = !fallback;
+            n_reads_records = dev_reads;
+        }
+        c->timer.add("bwa_device_fallback", 0.0, 0.0, fallback ? 1 : 0);
+    }
+    if (!on_device) { HostClock hc(c, "host_bwa_node_depth"); bwa_node_depth(c->nodes, reads); }
+    c->timer.add("bwa_reads_records", 0.0, 0.0, n_reads_records);
     c->snap[1].take(c->nodes, std::vector<Edge>(), nullptr);
     raw.clear();
     { HostClock hc(c, "host_bwa_raw_edges"); rc = bwa_raw_edges(c, hb, raw); }
     return rc;
 }
 
-// ExactBPConcordantSupport's counting loop (:3129-3166) over the host batch: `bps` sorted (chr, pos)
-int bwa_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& cov) {
-    if (!c->bwa) return fail(c, SQ_E_ARG, "sq_ingest_bwa_file first");
-    const HostBatch& hb = *c->bwa;
-    HostClock hc(c, "host_bwa_bp_support");
-    cov.assign(bps.size(), 0);
-    if (bps.empty()) return SQ_OK;
-    // which records the loop looks at at all is decided per record -- its own flags, its mate's place, its QNAME against the name set of the
-    // rebuilt fragments -- before the loop touches the one thing it carries (the cursor): decided side by side on the host threads (the
-    // name test, a binary search per record, was 6.5 s of one thread for C3's 50.8 M records), and the loop then walks the survivors
-    const std::vector<std::string>& names = c->chim_names;
-    auto in_names = [&](size_t ri) {  // std::binary_search(names, raw name) without building the std::string
+// ---- which records ExactBPConcordantSupport's loop looks at (:3136-3142)
+namespace {
+// std::binary_search(names, raw QNAME of a record) without building the std::string, behind one bit per name hash -- 15 k names in 4 M
+// bits; all but one record in a few thousand end there (the name test, a binary search per record, was 6.5 s of one thread for C3's 50.8 M records)
+struct NameTest {
+    const HostBatch& hb;
+    const std::vector<std::string>& names;
+    static constexpr size_t nbits = (size_t)1 << 22;
+    std::vector<uint64_t> maybe;
+    static unsigned long long hash_of(const char* p, size_t L) { unsigned long long h = 1469598103934665603ull; for (size_t i = 0; i < L; ++i) { h ^= (unsigned char)p[i]; h *= 1099511628211ull; } h ^= h >> 29; return h; }
+    NameTest(const HostBatch& hb, const std::vector<std::string>& names) : hb(hb), names(names) {
+        if (names.empty()) return;
+        maybe.assign(nbits / 64, 0);
+        for (const std::string& nm : names) { const unsigned long long h = hash_of(nm.data(), nm.size()) & (nbits - 1); maybe[h >> 6] |= 1ull << (h & 63); }
+    }
+    bool in_names(size_t ri) const {
         const char* p = hb.names.data() + hb.name_off[ri];
         const size_t L = hb.name_off[ri + 1] - hb.name_off[ri];
         size_t lo = 0, hi = names.size();
@@ -649,31 +743,82 @@ int bwa_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bp
             if (cmp < 0 || (cmp == 0 && m.size() < L)) lo = mid + 1; else hi = mid;
         }
         return lo < names.size() && names[lo].size() == L && std::memcmp(names[lo].data(), p, L) == 0;
-    };
-    // (in front of the binary search: one bit per name hash -- 15 k names in 4 M bits; all but one record in a few thousand end here)
-    auto hash_of = [](const char* p, size_t L) { unsigned long long h = 1469598103934665603ull; for (size_t i = 0; i < L; ++i) { h ^= (unsigned char)p[i]; h *= 1099511628211ull; } h ^= h >> 29; return h; };
-    const size_t nbits = (size_t)1 << 22;
-    std::vector<uint64_t> maybe(nbits / 64, 0);
-    for (const std::string& nm : names) { const unsigned long long h = hash_of(nm.data(), nm.size()) & (nbits - 1); maybe[h >> 6] |= 1ull << (h & 63); }
-    auto in_names_fast = [&](size_t ri) {
+    }
+    bool in_names_fast(size_t ri) const {
+        if (names.empty()) return false;
         const char* p = hb.names.data() + hb.name_off[ri];
         const unsigned long long h = hash_of(p, hb.name_off[ri + 1] - hb.name_off[ri]) & (nbits - 1);
         return ((maybe[h >> 6] >> (h & 63)) & 1) && in_names(ri);
-    };
-    const size_t nrec = hb.size();
-    std::vector<uint8_t> look(nrec, 0);
+    }
+};
+template <class F> void over_records(sq_ctx* c, size_t nrec, const F& f) {  // f(lo, hi) side by side on the host threads
+    if (c->pool && nrec > 100000) { const int np = 8 * (c->pool->size() + 1); c->pool->parallel_for(np, 1 << 20, [&](int k) { f(nrec * (size_t)k / (size_t)np, nrec * ((size_t)k + 1) / (size_t)np); }); }
+    else f(0, nrec);
+}
+}  // namespace
+// look[r] = 1: the loop looks at record r -- its own flags, its mate's place, its QNAME against the name set of the rebuilt fragments
+void bwa_look_bytes(sq_ctx* c, std::vector<uint8_t>& look) {
+    const HostBatch& hb = *c->bwa;
+    const NameTest nt(hb, c->chim_names);
+    look.assign(hb.size(), 0);
     auto decide = [&](size_t lo, size_t hi) {
         for (size_t ri = lo; ri < hi; ++ri) {
             const RecRef r{hb, ri};
             if (r.multi() || (int)hb.mapq[ri] < c->P.min_mapqual || r.dup() || !r.mapped() || r.refid() == -1) continue;
             const bool same_chr_mate = r.mate_mapped() && r.mrefid() == r.refid();
             if (same_chr_mate && (r.mpos() > r.pos() || (r.mpos() == r.pos() && (r.flag() & 0x80)))) continue;  // only the right-hand record of a pair
-            if (!names.empty() && in_names_fast(ri)) continue;
+            if (nt.in_names_fast(ri)) continue;
             look[ri] = 1;
         }
     };
-    if (c->pool && nrec > 100000) { const int np = 8 * (c->pool->size() + 1); c->pool->parallel_for(np, 1 << 20, [&](int k) { decide(nrec * (size_t)k / (size_t)np, nrec * ((size_t)k + 1) / (size_t)np); }); }
-    else decide(0, nrec);
+    over_records(c, hb.size(), decide);
+}
+// the name test alone, one byte per record (the device route: the names are on the host, the other factors are the class kernel's)
+void bwa_name_bytes(sq_ctx* c, std::vector<uint8_t>& in_names) {
+    const HostBatch& hb = *c->bwa;
+    const NameTest nt(hb, c->chim_names);
+    in_names.assign(hb.size(), 0);
+    over_records(c, hb.size(), [&](size_t lo, size_t hi) { for (size_t ri = lo; ri < hi; ++ri) in_names[ri] = nt.in_names_fast(ri) ? 1 : 0; });
+}
+// reads[r] = 1: record r feeds Reads (:871-881)
+void bwa_reads_bytes(const HostBatch& hb, std::vector<uint8_t>& reads) {
+    reads.assign(hb.size(), 0);
+    for (size_t ri = 0; ri < hb.size(); ++ri) reads[ri] = seed_record_passes(hb, ri) ? 1 : 0;
+}
+
+// the same count over the resident table (sq_bwa_on_device): the class kernel sets C_P3 behind the name test, once per graph, and the
+// breakpoint kernels of the STAR path walk the table
+int bwa_breakpoint_support_device(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& cov, bool count_row) {
+    if (!c->bwa || !c->bwa_dev_active) return fail(c, SQ_E_ARG, "internal: the --bwa table of this graph is not on the device");
+    if (!c->bwa_p3_ready) {
+        std::vector<uint8_t> in_names;
+        { HostClock hc(c, "host_bwa_name_test"); bwa_name_bytes(c, in_names); }
+        int64_t n_reads = 0, n_blocks = 0;
+        const int rc = dev_bwa_classify(c, in_names.data(), n_reads, c->bwa_n_p3, n_blocks);
+        if (rc) return rc;
+        c->bwa_p3_ready = true;
+    }
+    if (count_row) c->timer.add("bwa_bp_records", 0.0, 0.0, c->bwa_n_p3);
+    return dev_breakpoint_support(c, bps, cov);
+}
+
+// ExactBPConcordantSupport's counting loop (:3129-3166) over the host batch: `bps` sorted (chr, pos)
+int bwa_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& cov, bool count_row) {
+    if (!c->bwa) return fail(c, SQ_E_ARG, "sq_ingest_bwa_file first");
+    const HostBatch& hb = *c->bwa;
+    HostClock hc(c, "host_bwa_bp_support");
+    cov.assign(bps.size(), 0);
+    // which records the loop looks at at all is decided per record before the loop touches the one thing it carries (the cursor): decided
+    // side by side on the host threads, and the loop then walks the survivors
+    const size_t nrec = hb.size();
+    std::vector<uint8_t> look;
+    bwa_look_bytes(c, look);
+    if (count_row) {
+        std::atomic<int64_t> n_look{0};
+        over_records(c, nrec, [&](size_t lo, size_t hi) { int64_t k = 0; for (size_t ri = lo; ri < hi; ++ri) k += look[ri]; n_look += k; });
+        c->timer.add("bwa_bp_records", 0.0, 0.0, n_look.load());
+    }
+    if (bps.empty()) return SQ_OK;
     // The walk itself: the cursor moves one entry per record at most and never back (:3157), so where it stands depends on every record
     // before -- but it is a small number that a walk from 0 over a few ten thousand records in front of a stretch usually reproduces (two
     // cursors fed the same records never cross, and meet for good once the one behind has caught up).  Every stretch walks from such a

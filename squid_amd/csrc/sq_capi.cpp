@@ -694,8 +694,8 @@ static int call_sv(sq_ctx* c) {
         // (equal elements are indistinguishable pairs: any sort gives the reference's sorted list; the threaded introsort of sq_parsort.h)
         std_sort_parallel(BPs.begin(), BPs.end(), std::less<std::pair<int, int>>(), c->pool ? std::min(c->pool->size() + 1, 32) : 1, true);
         static const bool bp_host = env_set("SQUID_BP_HOST");  // debug cross-check of k_bp_walk
-        if (c->bwa) {  // (--bwa: the records and their names are on the host)
-            rc = bwa_breakpoint_support(c, BPs, cov);
+        if (c->bwa) {  // (--bwa: the records and their names are on the host; sq_bwa_on_device: the records are in HBM as well)
+            rc = c->bwa_dev_active ? bwa_breakpoint_support_device(c, BPs, cov) : bwa_breakpoint_support(c, BPs, cov);
             if (rc) return rc;
         } else if (!sh.on) {
             rc = bp_host ? dev_breakpoint_support_exact(c, BPs, cov) : dev_breakpoint_support(c, BPs, cov);
@@ -849,6 +849,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     c->P = *p;
     c->pool.reset(new HostPool(host_workers(p->world_size)));
     if (env_set("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = env_nonzero("SQUID_CHIM_STAGES_GPU") ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
+    if (env_set("SQUID_BWA_STAGES_GPU")) c->bwa_dev_env = env_nonzero("SQUID_BWA_STAGES_GPU") ? 1 : 0;    // the same for node depth / breakpoint support of a --bwa context
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
     *out = c;
@@ -1160,12 +1161,15 @@ static int sq_ingest_concordant_file_impl(sq_ctx* c, const char* path, int32_t n
 }
 int sq_ingest_concordant_file(sq_ctx* c, const char* path, int32_t n_threads) { return abi_guard(c, "sq_ingest_concordant_file", [&]() { return sq_ingest_concordant_file_impl(c, path, n_threads); }); }
 // `squid --bwa -b <bam>` (src/Config.cpp:98-100; src/main.cpp:33-37 runs without a chimeric file): every record of the one BAM file,
-// decoded on host threads with its QNAME, stays on the host; sq_build_graph then takes BuildNode_BWA / RawEdges (sq_bwa.cpp)
+// decoded with its QNAME, is kept on the host; sq_build_graph then takes BuildNode_BWA / RawEdges (sq_bwa.cpp) over that batch.  With
+// sq_bwa_on_device the first sq_build_graph also copies the batch into the device record table, where the node depth and the breakpoint
+// support are computed; the host batch stays where it is for the two automata
 static int sq_ingest_bwa_file_impl(sq_ctx* c, const char* path, int32_t n_threads) {
     if (!c || !path) return SQ_E_ARG;
     if (c->shard.on) return fail(c, SQ_E_ARG, "--bwa input is not chromosome-sharded");
     if (c->ref_len.empty()) return fail(c, SQ_E_ARG, "sq_set_references first");
     { int r0 = sq_set_source(c, path); if (r0) return r0; }
+    if (c->bwa_resident) { dev_clear_records(c); c->bwa_resident = false; c->bwa_dev_active = false; }  // (the device table of the batch before)
     std::shared_ptr<HostBatch> all = c->bwa_spare ? std::move(c->bwa_spare) : std::make_shared<HostBatch>();
     c->bwa_spare.reset();
     // (the arrays keep their storage -- and, on the way through the GPU reader, their sizes: every element is overwritten by the copy back)
@@ -1236,6 +1240,7 @@ int sq_clear_records(sq_ctx* c) {
     int rc = sq_reset(c);
     if (rc) return rc;
     dev_clear_records(c);
+    c->bwa_resident = false; c->bwa_dev_active = false;
     // (a --bwa batch is gigabytes in fourteen arrays: the context keeps its storage for the next --bwa ingest -- unmapping it and faulting
     // fresh pages in again was 0.25 s per sample at C3 --; sq_release_reader_buffers gives it back)
     if (c->bwa && c->bwa.use_count() == 1) c->bwa_spare = std::move(c->bwa);
@@ -1279,6 +1284,7 @@ size_t pad64(size_t n) { return (n + 63) & ~(size_t)63; }
 }  // namespace
 int sq_save_records(sq_ctx* c, const char* path) {
     if (!c || !path) return SQ_E_ARG;
+    if (c->bwa_resident) return fail(c, SQ_E_ARG, "the record cache is a STAR-mode file: the resident table of this context is a --bwa batch (sq_bwa_on_device)");
     HostBatch hb;
     int rc = dev_download_records(c, hb);
     if (rc) return rc;
@@ -1470,6 +1476,7 @@ int sq_reset(sq_ctx* c) {
     if (c->bp_future.valid()) (void)c->bp_future.get();
     dev_chim_drop_pending(c);
     c->chim_s2_pending = false; c->chim_s1_device = false;
+    c->bwa_dev_active = false;  // (the table stays resident: bwa_resident)
     copy_frags(c, c->frags0, c->frags);  // the graph stages trim the chimeric blocks in place, like the reference does
     c->nodes.clear(); c->edges.clear(); c->label.clear();
     c->graph_built = false; c->ordered = false;
@@ -1498,7 +1505,9 @@ int sq_debug_bp_support(sq_ctx* c, int32_t n_bp, const int32_t* chr, const int32
     for (int i = 0; i < n_bp; ++i) bps[i] = {chr[i], pos[i]};
     if (!std::is_sorted(bps.begin(), bps.end())) return fail(c, SQ_E_ARG, "breakpoints must be sorted by (chr, pos)");
     std::vector<int32_t> cov;
-    int rc = host_walk ? dev_breakpoint_support_exact(c, bps, cov) : dev_breakpoint_support(c, bps, cov);
+    int rc;
+    if (c->bwa && c->bwa_dev_active) rc = host_walk ? bwa_breakpoint_support(c, bps, cov, false) : bwa_breakpoint_support_device(c, bps, cov, false);  // (sq_bwa_on_device: the host loop / the kernels over the same batch)
+    else rc = host_walk ? dev_breakpoint_support_exact(c, bps, cov) : dev_breakpoint_support(c, bps, cov);
     dev_flush_timers(c);
     if (rc) return rc;
     std::copy(cov.begin(), cov.end(), coverage);
@@ -1508,6 +1517,29 @@ int sq_chimeric_on_device(sq_ctx* c, int32_t on) {
     if (!c) return SQ_E_ARG;
     c->chim_dev_asked = on != 0;  // (a --bwa context keeps the host route: chim_dev_on)
     return SQ_OK;
+}
+int sq_bwa_on_device(sq_ctx* c, int32_t on) {
+    if (!c) return SQ_E_ARG;
+    c->bwa_dev_asked = on != 0;  // (only a --bwa context looks at it: bwa_dev_on)
+    return SQ_OK;
+}
+static int sq_debug_bwa_depth_impl(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, int32_t* support, int32_t* sums, int64_t* out2) {
+    if (n_nodes < 0 || n_reads < 0 || (n_nodes && (!nodes3 || !support || !sums)) || (n_reads && !reads3) || !out2 || (route != 0 && route != 1) || (route == 1 && !c)) return SQ_E_ARG;
+    std::vector<int32_t> cnts, sm;
+    int64_t held = 0;
+    bool fallback = false;
+    if (route == 0) bwa_node_depth_flat(n_nodes, nodes3, n_reads, reads3, cnts, sm);  // (the loop itself: no cursor restated, nothing held to count)
+    else {
+        const int rc = dev_bwa_node_depth_flat(c, n_nodes, nodes3, n_reads, reads3, cnts, sm, held, fallback);
+        dev_flush_timers(c);
+        if (rc) return rc;
+    }
+    for (int32_t i = 0; i < n_nodes; ++i) { support[i] = cnts[(size_t)i]; sums[i] = sm[(size_t)i]; }
+    out2[0] = held; out2[1] = fallback ? 1 : 0;
+    return SQ_OK;
+}
+int sq_debug_bwa_depth(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, int32_t* support, int32_t* sums, int64_t* out2) {
+    return abi_guard(c, "sq_debug_bwa_depth", [&]() { return sq_debug_bwa_depth_impl(c, route, n_nodes, nodes3, n_reads, reads3, support, sums, out2); });
 }
 static int sq_debug_chim_stages_impl(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
                                      const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8) {

@@ -284,6 +284,14 @@ struct sq_ctx {
     bool chim_s1_device = false;      // this graph's RawEdgesChim ran on the device: c->frags is untrimmed, the trimmed blocks are in HBM
     bool chim_s2_pending = false;     // ExactBreakpoint is queued on the stream (dev_exact_breakpoints_start); sq_call_sv collects it
     bool chim_dev_on() const { return !bwa && (chim_dev_env >= 0 ? chim_dev_env != 0 : chim_dev_asked); }
+    // --bwa: node depth and breakpoint support on the device (sq_bwa_on_device; SQUID_BWA_STAGES_GPU=1 / =0, read by sq_create, forces / forbids it)
+    bool bwa_dev_asked = false;       // what the call said
+    int bwa_dev_env = -1;             // the override: -1 none
+    bool bwa_resident = false;        // the device record table holds this --bwa batch (made by the first sq_build_graph that finds the route on; kept across sq_reset)
+    bool bwa_dev_active = false;      // this graph's build had the table and its class bytes: sq_call_sv counts the breakpoint support there
+    bool bwa_p3_ready = false;        // the class bytes carry C_P3 for this graph's fragment names
+    int64_t bwa_n_p3 = 0;             // records with C_P3
+    bool bwa_dev_on() const { return bwa && (bwa_dev_env >= 0 ? bwa_dev_env != 0 : bwa_dev_asked); }
     // concordant side (device)
     sq::DeviceRecords* dev = nullptr;
     // --bwa (sq_ingest_bwa_file): every record of the one BAM file on the host, with its QNAME (sq_bwa.cpp)
@@ -443,7 +451,13 @@ int chimeric_fragments_host(sq_ctx* c, const char* path, int threads);
 int junction_sequences(sq_ctx* c, const std::vector<std::string>& ref_names, const char* bedpe, const char* fasta, const char* out_prefix);
 // ---- sq_bwa.cpp (`squid --bwa`)
 int bwa_nodes_and_edges(sq_ctx* c, std::vector<Edge>& raw);  // BuildNode_BWA + RawEdges over the host batch: c->nodes (+ snapshot 1), c->frags, raw edges
-int bwa_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& cov);
+int bwa_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& cov, bool count_row = true);  // count_row: the timer row bwa_bp_records
+int bwa_breakpoint_support_device(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& cov, bool count_row = true);  // sq_bwa_on_device: over the resident table
+void bwa_look_bytes(sq_ctx* c, std::vector<uint8_t>& look);          // per record: ExactBPConcordantSupport's loop looks at it (decide())
+void bwa_name_bytes(sq_ctx* c, std::vector<uint8_t>& in_names);      // per record: the raw QNAME is in the name set of the rebuilt fragments
+void bwa_reads_bytes(const HostBatch& hb, std::vector<uint8_t>& reads);  // per record: it feeds Reads (seed_record_passes)
+void bwa_set_node_depths(std::vector<Node>& N, const std::vector<int32_t>& cnts, const std::vector<int32_t>& sums);
+void bwa_node_depth_flat(int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums);  // the depth loop on flat tables
 void reduce_edges(std::vector<Edge>& raw, std::vector<Edge>& out, int threads = 1);
 void filter_by_weight(sq_ctx* c);
 void filter_by_interleaving(sq_ctx* c, std::vector<uint8_t>& keep);
@@ -504,6 +518,13 @@ int dev_chimeric_edges(sq_ctx* c, std::vector<Edge>& raw, bool& fallback);
 int dev_exact_breakpoints_start(sq_ctx* c, bool& fallback);  // queued behind the final graph; ..._collect waits for its event
 int dev_exact_breakpoints_collect(sq_ctx* c, BPMap& bp);
 void dev_chim_drop_pending(sq_ctx* c);
+// --bwa on the device (sq_bwa_stage.inc): the host batch into the record table; the class byte of every record (in_names: one host byte per
+// record or null, see bws::class_of) with the counts of READS records, C_P3 records and Reads blocks; the node depth kernels over the
+// table behind dev_upload_nodes (fallback: a chromosome goes down along Reads, nothing is returned); the same kernels on flat tables
+int dev_bwa_upload(sq_ctx* c, const HostBatch& hb);
+int dev_bwa_classify(sq_ctx* c, const uint8_t* in_names, int64_t& n_reads, int64_t& n_p3, int64_t& n_reads_blocks);
+int dev_bwa_node_depth(sq_ctx* c, int n_nodes, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback);
+int dev_bwa_node_depth_flat(sq_ctx* c, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback);
 int dev_chim_download_trimmed(sq_ctx* c);  // the blocks as the device trimmed them, into c->frags
 int dev_connected_components(sq_ctx* c, int n_nodes, const std::vector<Edge>& edges, std::vector<int32_t>& label);
 struct SmallProblem { int n; int eoff, ecount; };  // edges: local u,v,hu,hv,w packed as 5 ints each

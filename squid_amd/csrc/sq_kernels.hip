@@ -35,6 +35,7 @@
 #include "sq_inflate_spec.inc"
 #include "sq_resolve.inc"
 #include "sq_chim_stage.inc"
+#include "sq_bwa_stage.inc"
 
 #define HIPCHK(call)                                                                                         \
     do {                                                                                                     \
@@ -292,6 +293,11 @@ struct DeviceRecords {
     int64_t p2_valid_n = -1;                    // records the list was made for (-1: none)
     DBuf<unsigned long long> bp_key, bp_front;  // breakpoint cursor: largest (chromosome, fragment start) per 256 records (k_edges_near) / in front of every tile of k_bp2
     int64_t bp_key_n = -1;                      // record count the keys were made for
+    // --bwa on the device (sq_bwa_stage.inc): chromosome of every block of a READS record (-1: not in Reads), the name-test bytes, tile maxima
+    // and prefixes of the depth kernels, count | sum per node + the two counters
+    DBuf<int32_t> bwa_blk_chr, bwa_tmax, bwa_front;
+    DBuf<uint8_t> bwa_names;
+    DBuf<uint32_t> bwa_acc;
     // pass 1 (k_pass1): look-back status words, kept records in front of every tile, tile sort keys, the three lists, scalars
     DBuf<int32_t> tile_cnt, tile_K, tile_zcnt2, zc_v, zc_K, zc_refid, zc_pos;
     DBuf<unsigned long long> tile_ob, zc_ob;  // tile_ob: [ntiles] pair of every tile | [ntiles] pair in front of every tile
@@ -321,6 +327,8 @@ struct DeviceRecords {
 
 // classification bits (cls)
 enum : uint8_t { C_P2 = 1, C_P1 = 2, C_P3 = 4, C_CONC = 8, C_PART = 16, C_HASSTUB = 32 };
+static_assert(bws::CLS_P3 == C_P3 && (bws::CLS_READS & (C_P2 | C_P1 | C_P3 | C_CONC | C_PART | C_HASSTUB)) == 0, "the --bwa class byte shares C_P3 with the record kernels");
+static_assert(bws::AUX_MULTI == SQ_AUX_MULTI && bws::FINE_SHIFT == NODE_FINE_SHIFT, "sq_bwa_stage.inc restates these");
 // keep bits
 enum : uint8_t { K_1 = 1, K_2 = 2, K_BUILD = 4, K_P3 = 8 /* copy of the class bit C_P3: the edge stage makes the breakpoint-cursor keys without reading the class byte */ };
 
@@ -3064,6 +3072,7 @@ void dev_destroy(sq_ctx* c) {
     if (!c->dev) return;
     DeviceRecords& D = *c->dev;
     D.chim.release();
+    D.bwa_blk_chr.release(); D.bwa_tmax.release(); D.bwa_front.release(); D.bwa_names.release(); D.bwa_acc.release();
     D.refid.release(); D.pos.release(); D.mrefid.release(); D.mpos.release(); D.endpos.release(); D.b_refpos.release(); D.b_matchref.release();
     D.b_pack.release(); D.n_pack.release(); D.r_pack.release();
     D.flag.release(); D.totlen.release(); D.b_readpos.release(); D.b_matchread.release(); D.mapq.release(); D.aux.release(); D.blk_off.release();
@@ -5199,6 +5208,141 @@ void dev_chim_drop_pending(sq_ctx* c) {
     ChimStage& S = c->dev->chim;
     if (S.done && S.h_out) (void)hipEventSynchronize(S.done);
     S.h_out = nullptr;
+}
+
+// ------------------------------------------------------------------------------------------------ --bwa on the device (sq_bwa_stage.inc)
+__global__ __launch_bounds__(256) void k_bwa_classify(bws::Recs R, int min_mapqual, const uint8_t* in_names, uint8_t* cls, int32_t* blk_chr, uint32_t* counts /* READS records, C_P3 records, Reads blocks */) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint8_t cl = 0;
+    uint32_t nblk = 0;
+    if (r < R.n) {
+        bws::classify(R, min_mapqual, in_names, cls, blk_chr, r);
+        cl = cls[r];
+        if (cl & bws::CLS_READS) nblk = R.blk_off[r + 1] - R.blk_off[r];
+    }
+    const uint32_t n_reads = (uint32_t)__popcll(__ballot(cl & bws::CLS_READS)), n_p3 = (uint32_t)__popcll(__ballot(cl & bws::CLS_P3));
+    const uint32_t blocks = wv::scan_incl_add(nblk);
+    if ((threadIdx.x & 63) == 63) {
+        if (n_reads) atomicAdd(counts, n_reads);
+        if (n_p3) atomicAdd(counts + 1, n_p3);
+        if (blocks) atomicAdd(counts + 2, blocks);
+    }
+}
+__global__ __launch_bounds__(256) void k_bwa_depth_max(bws::Nodes N, bws::Blocks B, int64_t ntiles, int32_t* tmax) {
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per tile
+    if (tile >= ntiles) return;
+    bws::depth_tile_max(N, B, tile, tmax);
+}
+__global__ __launch_bounds__(64) void k_bwa_depth_prefix(int64_t ntiles, const int32_t* tmax, int32_t* front) { bws::depth_prefix(ntiles, tmax, front); }
+__global__ __launch_bounds__(256) void k_bwa_depth_apply(bws::Nodes N, bws::Blocks B, int64_t ntiles, const int32_t* front, uint32_t* support, uint32_t* sum, uint32_t* counters) {
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    bws::depth_tile_apply(N, B, tile, front, support, sum, counters);
+}
+__global__ void k_bwa_pack_reads(int64_t n, const int32_t* reads3, int32_t* chr, int4* pack) {  // flat Reads triples as the block arrays hold them
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    chr[j] = reads3[3 * j];
+    pack[j] = make_int4(reads3[3 * j + 1], reads3[3 * j + 2], 0, 0);
+}
+
+int dev_bwa_upload(sq_ctx* c, const HostBatch& hb) {
+    HIPCHK(hipSetDevice(c->P.device));
+    dev_clear_records(c);
+    if (hb.size() >= 0x7fffffffull) return fail(c, SQ_E_CAPACITY, "more than 2^31 records for the device table of a --bwa batch");
+    sq_aln_batch b;
+    hb.view(&b, false);
+    return dev_append_records(c, &b);
+}
+
+int dev_bwa_classify(sq_ctx* c, const uint8_t* in_names, int64_t& n_reads, int64_t& n_p3, int64_t& n_reads_blocks) {
+    DeviceRecords& D = *c->dev;
+    hipStream_t s = c->stream;
+    const int64_t n = D.n;
+    n_reads = n_p3 = n_reads_blocks = 0;
+    HIPCHK(D.cls.reserve((size_t)n + 4)); HIPCHK(D.bwa_blk_chr.reserve((size_t)D.nb + 4));
+    D.bp_key_n = -1;  // (the breakpoint cursor keys follow the class bytes)
+    if (!n) return SQ_OK;
+    if (in_names) {
+        HIPCHK(D.bwa_names.reserve((size_t)n));
+        EvTimer t(c, "bwa_names_upload", (double)n);
+        HIPCHK(hipMemcpyAsync(D.bwa_names.p, in_names, (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    uint32_t* counts = (uint32_t*)D.flags.p + 40;
+    HIPCHK(hipMemsetAsync(counts, 0, 3 * sizeof(uint32_t), s));
+    const RecView V = D.view();
+    const bws::Recs R{n, V.refid, V.pos, V.mrefid, V.mpos, V.flag, V.mapq, V.aux, V.blk_off};
+    { EvTimer t(c, "k_bwa_classify", 22.0 * n + (in_names ? 0.0 : 4.0 * D.nb));
+      // (the chromosome per block is written with the READS bit; the second launch of a graph only adds C_P3)
+      hipLaunchKernelGGL(k_bwa_classify, grid_for(n, 256), dim3(256), 0, s, R, (int)c->P.min_mapqual, in_names ? D.bwa_names.p : (const uint8_t*)nullptr, D.cls.p, in_names ? (int32_t*)nullptr : D.bwa_blk_chr.p, counts); }
+    uint32_t h[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(h, counts, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    n_reads = h[0]; n_p3 = h[1]; n_reads_blocks = h[2];
+    return SQ_OK;
+}
+
+// the three launches over nb blocks; acc = support (n_nodes) | sum (n_nodes) | counters (2), zeroed here
+static int bwa_depth_launch(sq_ctx* c, const bws::Nodes& N, const bws::Blocks& B, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback) {
+    DeviceRecords& D = *c->dev;
+    hipStream_t s = c->stream;
+    const size_t nn = (size_t)N.n;
+    const int64_t ntiles = (B.nb + bws::TILE_BLOCKS - 1) / bws::TILE_BLOCKS;
+    cnts.assign(nn, 0); sums.assign(nn, 0); held = 0; fallback = false;
+    if (!ntiles || !nn) return SQ_OK;
+    HIPCHK(D.bwa_tmax.reserve(2 * (size_t)ntiles)); HIPCHK(D.bwa_front.reserve(2 * (size_t)ntiles)); HIPCHK(D.bwa_acc.reserve(2 * nn + 2));
+    HIPCHK(hipMemsetAsync(D.bwa_acc.p, 0, (2 * nn + 2) * sizeof(uint32_t), s));
+    const dim3 grid((unsigned)((ntiles + 3) / 4));
+    { EvTimer t(c, "k_bwa_depth_max", 20.0 * B.nb);
+      hipLaunchKernelGGL(k_bwa_depth_max, grid, dim3(256), 0, s, N, B, ntiles, D.bwa_tmax.p); }
+    { EvTimer t(c, "k_bwa_depth_prefix", 16.0 * ntiles);
+      hipLaunchKernelGGL(k_bwa_depth_prefix, dim3(1), dim3(64), 0, s, ntiles, D.bwa_tmax.p, D.bwa_front.p); }
+    { EvTimer t(c, "k_bwa_depth_apply", 20.0 * B.nb);
+      hipLaunchKernelGGL(k_bwa_depth_apply, grid, dim3(256), 0, s, N, B, ntiles, D.bwa_front.p, D.bwa_acc.p, D.bwa_acc.p + nn, D.bwa_acc.p + 2 * nn); }
+    std::vector<uint32_t> h(2 * nn + 2);
+    HIPCHK(hipMemcpyAsync(h.data(), D.bwa_acc.p, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    fallback = h[2 * nn + bws::CNT_DECREASING] != 0;
+    held = h[2 * nn + bws::CNT_HELD];
+    for (size_t i = 0; i < nn; ++i) { cnts[i] = (int32_t)h[i]; sums[i] = (int32_t)h[nn + i]; }
+    return SQ_OK;
+}
+int dev_bwa_node_depth(sq_ctx* c, int n_nodes, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback) {
+    DeviceRecords& D = *c->dev;
+    const NodeView& nv = D.nv;
+    if (nv.n != n_nodes || nv.n_ref != (int)c->ref_len.size()) return fail(c, SQ_E_ARG, "internal: --bwa node depth before the node table was uploaded");
+    const bws::Nodes N{nv.n, nv.n_ref, nv.chr, nv.pos, nv.len, nv.chr_start, nv.fine, nv.fine_off};
+    const bws::Blocks B{D.nb, D.bwa_blk_chr.p, (const uint32_t*)D.b_pack.p};
+    return bwa_depth_launch(c, N, B, cnts, sums, held, fallback);
+}
+int dev_bwa_node_depth_flat(sq_ctx* c, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback) {
+    hipStream_t s = c->stream;
+    const size_t nn = (size_t)n_nodes, nr = (size_t)n_reads;
+    int n_ref = 0;
+    for (size_t i = 0; i < nn; ++i) {
+        if (nodes3[3 * i] < 0 || (i && nodes3[3 * i] < nodes3[3 * (i - 1)])) return fail(c, SQ_E_ARG, "sq_debug_bwa_depth: node chromosomes must be non-negative and sorted");
+        n_ref = std::max(n_ref, nodes3[3 * i] + 1);
+    }
+    // chr | pos | len | chr_start, then the Reads triples; no position index (bws::first_node_behind bisects the chromosome)
+    std::vector<int32_t> h(3 * nn + (size_t)n_ref + 1 + 3 * nr);
+    for (size_t i = 0; i < nn; ++i) { h[i] = nodes3[3 * i]; h[nn + i] = nodes3[3 * i + 1]; h[2 * nn + i] = nodes3[3 * i + 2]; }
+    { size_t j = 0; for (int k = 0; k <= n_ref; ++k) { while (j < nn && nodes3[3 * j] < k) ++j; h[3 * nn + (size_t)k] = (int32_t)j; } }
+    if (nr) std::memcpy(h.data() + 3 * nn + n_ref + 1, reads3, 3 * nr * sizeof(int32_t));
+    DBuf<int32_t> tab, chr;
+    DBuf<int4> pack;
+    int rc = SQ_OK;
+    auto run = [&]() -> int {
+        HIPCHK(tab.reserve(h.size() + 1)); HIPCHK(chr.reserve(nr + 1)); HIPCHK(pack.reserve(nr + 1));
+        HIPCHK(hipMemcpyAsync(tab.p, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        if (nr) hipLaunchKernelGGL(k_bwa_pack_reads, grid_for((int64_t)nr, 256), dim3(256), 0, s, (int64_t)nr, tab.p + 3 * nn + n_ref + 1, chr.p, pack.p);
+        const bws::Nodes N{n_nodes, n_ref, tab.p, tab.p + nn, tab.p + 2 * nn, tab.p + 3 * nn, nullptr, nullptr};
+        const bws::Blocks B{(int64_t)nr, chr.p, (const uint32_t*)pack.p};
+        return bwa_depth_launch(c, N, B, cnts, sums, held, fallback);
+    };
+    rc = run();
+    (void)hipStreamSynchronize(s);
+    tab.release(); chr.release(); pack.release();
+    return rc;
 }
 
 #include "sq_graph_kernels.inc"

@@ -62,6 +62,15 @@ WV_FN uint32_t scan_incl_add(uint32_t v) {
     rendezvous(7);
     return r;
 }
+WV_FN int32_t scan_incl_max(int32_t v) {
+    Emu* e = emu();
+    e->x[e->cur] = (uint32_t)v;
+    rendezvous(8);
+    int32_t r = v;
+    for (int i = 0; i < e->cur; ++i) if ((int32_t)(uint32_t)e->x[i] > r) r = (int32_t)(uint32_t)e->x[i];
+    rendezvous(9);
+    return r;
+}
 WV_FN unsigned long long lanemask_lt() { return lane() ? (~0ull >> (64 - lane())) : 0ull; }
 WV_FN uint32_t uniform(uint32_t v) { return v; }
 WV_FN int popc64(unsigned long long m) { return __builtin_popcountll(m); }
@@ -135,6 +144,17 @@ WV_FN uint32_t scan_incl_add(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);  // row_shr:8
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
+    return x;
+}
+WV_FN int32_t scan_incl_max(int32_t x) {  // (signed; lanes without a source keep `old` = the identity)
+    const int lo = (int)0x80000000;
+    int y;
+    y = __builtin_amdgcn_update_dpp(lo, x, 0x111, 0xf, 0xf, false); x = y > x ? y : x;  // row_shr:1
+    y = __builtin_amdgcn_update_dpp(lo, x, 0x112, 0xf, 0xf, false); x = y > x ? y : x;  // row_shr:2
+    y = __builtin_amdgcn_update_dpp(lo, x, 0x114, 0xf, 0xf, false); x = y > x ? y : x;  // row_shr:4
+    y = __builtin_amdgcn_update_dpp(lo, x, 0x118, 0xf, 0xf, false); x = y > x ? y : x;  // row_shr:8
+    y = __builtin_amdgcn_update_dpp(lo, x, 0x142, 0xa, 0xf, false); x = y > x ? y : x;  // row_bcast:15 -> rows 1, 3
+    y = __builtin_amdgcn_update_dpp(lo, x, 0x143, 0xc, 0xf, false); x = y > x ? y : x;  // row_bcast:31 -> rows 2, 3
     return x;
 }
 WV_FN unsigned long long lanemask_lt() { return ~0ull >> 1 >> (63 - lane()); }
