@@ -17,7 +17,7 @@
 // inside their own leaf of at most sixteen) gives what the one pass over everything gives.  A comparator that is not a strict weak order
 // (the reference's FrontSmallerThan, ReadRec.cpp:382) offers no such guarantee and keeps the single pass.
 // The pieces are libstdc++'s own (bits/stl_algo.h, GCC 11: __unguarded_partition_pivot, __introsort_loop, __partial_sort,
-// __final_insertion_sort), called directly.  tests/test_host_logic.py compares with std::sort on tie-heavy inputs (sq_debug_parsort).
+// __final_insertion_sort), called directly.  tests/parsort_check.cpp compares with std::sort on tie-heavy inputs.
 #pragma once
 #include <algorithm>
 #include <atomic>

@@ -9,9 +9,9 @@
 // boundaries supported by split-read triplets and discordant pairs.
 //
 // Shape knobs (--read-len, --insert, --clip-frac, --clip-len, --multi-frac, --dup-frac, --lowq-frac, --pcrcopy-frac, --polya-frac,
-// --odd-pair-frac, --split-anchor, --contigs) vary what the layout above keeps fixed.  Every draw a knob needs comes from a second
-// stream (`krng`), and only when the knob is given: without knobs the files are byte for byte what they were before the knobs existed
-// (pinned by tests/golden/synth_default_sha256.json).
+// --odd-pair-frac, --split-anchor, --contigs, and --bwa-mapq in --bwa mode) vary what the layout above keeps fixed.  Every draw a knob
+// needs comes from a second stream (`krng`), and only when the knob is given: without knobs the files are byte for byte what they were
+// before the knobs existed (pinned by tests/golden/synth_default_sha256.json).
 //
 // This file is input tooling: it is NOT part of the product data path and not part of oracle/.
 
@@ -149,6 +149,10 @@ int reg2bin(int beg, int end) {
 // a hard-clipped SUPPLEMENTARY record (0x800) of the same name and mate, every record knows its mate, and the junction-supporting
 // fragments sit in the sorted stream among the concordant ones (no second file).
 static bool g_bwa = false;
+// --bwa-mapq LO,HI (--bwa only): a record that would get MAPQ 60 gets a value uniform in [LO, HI], drawn from the knob stream; multi-mappers
+// keep 0.  Not given (lo < 0): 60, and no draw
+static int g_bwa_mapq_lo = -1, g_bwa_mapq_hi = -1;
+static long g_bwa_mapq_below_30 = 0;
 
 struct Rec {
     int32_t refid, pos;
@@ -159,6 +163,7 @@ void put32(std::vector<uint8_t>& v, int32_t x) { for (int i = 0; i < 4; ++i) v.p
 void put16(std::vector<uint8_t>& v, int x) { v.push_back(x & 0xff); v.push_back((x >> 8) & 0xff); }
 
 // seqlen = number of bases stored (hard clips excluded)
+int bwa_mapq_draw();  // (from main's knob stream; defined in front of main)
 Rec make_record(Rng& rng, const std::string& name, int refid, int pos, int mapq, int flag,
                 const std::vector<CigarOp>& cigar, int mrefid, int mpos, int tlen, int nh, bool lowqual_run) {
     Rec r;
@@ -174,7 +179,7 @@ Rec make_record(Rng& rng, const std::string& name, int refid, int pos, int mapq,
     put32(b, refid);
     put32(b, pos);
     b.push_back((uint8_t)(name.size() + 1));
-    if (g_bwa) mapq = mapq >= 255 ? 60 : 0;
+    if (g_bwa) mapq = mapq >= 255 ? (g_bwa_mapq_lo < 0 ? 60 : bwa_mapq_draw()) : 0;
     b.push_back((uint8_t)mapq);
     put16(b, reg2bin(pos, pos + std::max(reflen, 1)));
     put16(b, (int)cigar.size());
@@ -320,6 +325,13 @@ struct Tsv {
 
 struct ChimEmit { std::vector<Rec> recs; };
 
+Rng* g_krng = nullptr;
+int bwa_mapq_draw() {
+    const int q = g_krng->range(g_bwa_mapq_lo, g_bwa_mapq_hi);
+    if (q < 30) ++g_bwa_mapq_below_30;
+    return q;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -342,6 +354,7 @@ int main(int argc, char** argv) {
     double polya_frac = 0, odd_frac = 0;         // --polya-frac, --odd-pair-frac
     int anchor_lo = 25, anchor_hi = 75;          // --split-anchor LO,HI
     std::string contigs_arg;                     // --contigs "LEN,LEN,..." (config T2)
+    bool bwa_mapq_set = false;                   // --bwa-mapq LO,HI (--bwa)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto val = [&]() { return std::string(i + 1 < argc ? argv[++i] : ""); };
@@ -370,6 +383,7 @@ int main(int argc, char** argv) {
         else if (a == "--odd-pair-frac") odd_frac = std::atof(val().c_str());
         else if (a == "--split-anchor") { const auto p = parse_pair<int>(val()); anchor_lo = p.first; anchor_hi = p.second; }
         else if (a == "--contigs") contigs_arg = val();
+        else if (a == "--bwa-mapq") { const auto p = parse_pair<int>(val()); g_bwa_mapq_lo = p.first; g_bwa_mapq_hi = p.second; bwa_mapq_set = true; }
         else { std::fprintf(stderr, "unknown arg %s\n", a.c_str()); return 2; }
     }
     std::vector<Contig> contigs;
@@ -409,6 +423,9 @@ int main(int argc, char** argv) {
     Rng krng(seed ^ 0x5A4B4E4F42ull);  // every draw of a shape knob; untouched when no knob is given
     if (RL < 40 || RL > 1000 || ins_sd < 0 || clip_lo < 1 || clip_hi < clip_lo || anchor_lo < 1 || anchor_hi < anchor_lo) { std::fprintf(stderr, "bad shape knob\n"); return 2; }
     if (!contigs_arg.empty() && config != "T2") { std::fprintf(stderr, "--contigs needs --config T2\n"); return 2; }
+    if (bwa_mapq_set && !g_bwa) { std::fprintf(stderr, "--bwa-mapq needs --bwa\n"); return 2; }
+    if (bwa_mapq_set && (g_bwa_mapq_lo < 0 || g_bwa_mapq_hi < g_bwa_mapq_lo || g_bwa_mapq_hi > 60)) { std::fprintf(stderr, "--bwa-mapq: 0 <= LO <= HI <= 60\n"); return 2; }
+    g_krng = &krng;
     // a split read keeps at least 20 bases on either side (the floor a piece has anyway); 25..75 of 100 bases is inside that
     anchor_hi = std::min(anchor_hi, RL - 20);
     anchor_lo = std::min(anchor_lo, anchor_hi);
@@ -872,6 +889,8 @@ int main(int argc, char** argv) {
     // one count per planted kind (fragments of the concordant file; polya_reads counts records of both files)
     std::printf(",\"read_len\":%d,\"short_clips\":%ld,\"long_clips\":%ld,\"polya_reads\":%ld,\"overlapping_mates\":%ld", RL, n_short_clips, n_long_clips, n_polya, n_overlap);
     for (int k = 0; k < ODD_KINDS; ++k) std::printf(",\"%s\":%ld", odd_names[k], n_odd[k]);
-    std::printf(",\"multi\":%ld,\"dup\":%ld,\"lowq\":%ld,\"pcrcopy\":%ld}\n", n_multi, n_dup, n_lowq, n_pcrcopy);
+    std::printf(",\"multi\":%ld,\"dup\":%ld,\"lowq\":%ld,\"pcrcopy\":%ld", n_multi, n_dup, n_lowq, n_pcrcopy);
+    if (bwa_mapq_set) std::printf(",\"bwa_mapq_below_30\":%ld", g_bwa_mapq_below_30);  // (records; the line is unchanged without the knob)
+    std::printf("}\n");
     return 0;
 }

@@ -1,7 +1,7 @@
 """One place that turns a seed into a test case for the random-shape tests (tests/test_random_shapes.py and the shape cases of the
 literal-loop tests): generator arguments that vary what the generator's defaults keep fixed (read length, insert size, clip lengths on
 both sides of the 15-base threshold, pair flags, poly-A blocks, filter rates, contig lists), oracle flags, and the matching
-squid_amd.Context keyword arguments.
+squid_amd.Context keyword arguments.  draw_bwa does the same for `squid --bwa` (tests/test_random_shapes_bwa.py).
 
 A plain module, not a conftest: nothing here changes how the suite runs."""
 import gzip
@@ -54,17 +54,53 @@ def draw(seed):
         lens = [r.randint(900000, 3000000) for _ in range(r.randint(2, 4))] + [r.randint(20000, 80000) for _ in range(r.randint(1, 2))]
         r.shuffle(lens)
         gen += ["--contigs", ",".join(str(x) for x in lens)]
+    flags, params = _draw_flags(r, lambda: r.randint(1, 4))
+    return tuple(gen), flags, params
+
+
+def _draw_flags(r, mapqual, p_mapqual=0.3):
+    """(oracle flags, Context keywords), each flag with probability 0.3 (-mq: p_mapqual)"""
     flags, params = [], {}
     # (flag, keyword, draw): between the reference's default and the value PARAM_SETS of tests/test_gpu_parity.py uses
     for flag, kw, val in (("-w", "min_edge_weight", lambda: r.randint(1, 5)), ("-r", "discordant_ratio", lambda: r.choice([1.5, 2.0, 4.0, 8.0])),
                           ("-a", "max_allowed_degree", lambda: r.choice([5, 10, 50])), ("-dp", "concord_dist_pos", lambda: r.choice([2000, 10000, 50000])),
-                          ("-di", "concord_dist_idx", lambda: r.choice([3, 10, 20])), ("-mq", "min_mapqual", lambda: r.randint(1, 4)),
+                          ("-di", "concord_dist_idx", lambda: r.choice([3, 10, 20])), ("-mq", "min_mapqual", mapqual),
                           ("-pl", "max_lowphred_len", lambda: r.choice([5, 10])), ("-pm", "min_phred", lambda: r.choice([4, 10]))):
-        if r.random() < 0.3:
+        if r.random() < (p_mapqual if flag == "-mq" else 0.3):
             v = val()
             flags += [flag, str(v)]
             params[kw] = v
-    return tuple(gen), tuple(flags), params
+    return tuple(flags), params
+
+
+BWA_MQ = (1, 10, 30, 45, 60)
+
+
+def draw_bwa(seed):
+    """seed -> (gen_args, oracle_flags, context_params) for `--bwa`: the generator arguments of draw(seed) in the shape `bwa mem` writes, in about
+    half the cases with MAPQ spread over [LO, HI] (LO 1-20, HI 40-60) instead of 60; the flags from a stream of their own (draw() and its 24
+    cases stay what they are), -mq from BWA_MQ so that it cuts inside that range -- with the spread twice as often as the other flags, since
+    that is where it separates three classes of records, and never above HI, where no record would be left for the breakpoint support; the
+    keywords as every --bwa test passes them"""
+    gen = list(draw(seed)[0])
+    r = random.Random(f"bwa {seed}")
+    gen += ["--bwa"]
+    hi = None
+    if r.random() < 0.5:
+        hi = r.randint(40, 60)
+        gen += ["--bwa-mapq", f"{r.randint(1, 20)},{hi}"]
+    flags, params = _draw_flags(r, lambda: r.choice([q for q in BWA_MQ if hi is None or q <= hi]), 0.6 if hi else 0.3)
+    params.setdefault("min_mapqual", 1)
+    params["star_mapq"] = False
+    return tuple(gen), flags, params
+
+
+def mapq_range(gen_args):
+    """(LO, HI) of --bwa-mapq, or None"""
+    if "--bwa-mapq" not in gen_args:
+        return None
+    lo, hi = gen_args[gen_args.index("--bwa-mapq") + 1].split(",")
+    return int(lo), int(hi)
 
 
 def insert_mean(gen_args):
@@ -82,10 +118,21 @@ def generate(build_dir, prefix, gen_args, config="T2"):
 
 
 def commands(build_dir, prefix, gen_args, flags, config="T2"):
-    """the two command lines that rebuild a case on the CPU (for assertion messages)"""
+    """the two command lines that rebuild a case on the CPU (for assertion messages); the `--bwa` form when the generator gets --bwa"""
     b = Path(build_dir)
+    files = ["--bwa", "-b", f"{prefix}.bam"] if "--bwa" in gen_args else ["-b", f"{prefix}.bam", "-c", f"{prefix}.chim.bam"]
     return (" ".join([str(b / "gen_synth_bam"), "--config", config, "--out", str(prefix), *gen_args]) + "\n" +
-            " ".join([str(b / "squid_oracle"), "-b", f"{prefix}.bam", "-c", f"{prefix}.chim.bam", "-o", "oracle", "--dump", "dump", *flags]))
+            " ".join([str(b / "squid_oracle"), *files, "-o", "oracle", "--dump", "dump", *flags]))
+
+
+def run_oracle_bwa(build_dir, prefix, outdir, flags):
+    """squid_oracle --bwa with stage dumps -> (exit status, sv path, dump dir)"""
+    outdir = Path(outdir)
+    dump = outdir / "dump"
+    dump.mkdir(parents=True, exist_ok=True)
+    rc = subprocess.call([str(Path(build_dir) / "squid_oracle"), "--bwa", "-b", f"{prefix}.bam", "-o", str(outdir / "oracle"), "--dump", str(dump), *flags],
+                         stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return rc, outdir / "oracle_sv.txt", dump
 
 
 def usable(sv_path, dump):
@@ -100,6 +147,10 @@ def usable(sv_path, dump):
 # (tests/golden/make_shape_seeds.py): a seed is kept when the generator exits 0, the oracle exits 0 (4 = a reference assert), no
 # ordering problem is ambiguous and _sv.txt has a call.  test_every_seed_is_usable repeats the conditions.
 SEEDS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24]
+
+# ---- the 16 cases of tests/test_random_shapes_bwa.py, found the same way (make_shape_seeds.py --bwa: draw_bwa and squid_oracle --bwa, and at
+# least one rebuilt fragment); test_every_bwa_seed_is_usable repeats the conditions.  Seed 6 has more than 65 536 blocks in Reads.
+BWA_SEEDS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16]
 
 # six of them for the literal-loop readings: together they hold odd pairs, short clips, overlapping mates, poly-A blocks and read
 # lengths other than 100

@@ -9,9 +9,11 @@ import pytest
 
 import bamwriter as bw
 import oracle_util as ou
+import shapes
 import squid_amd
 from test_bwa import _oracle_bwa
-from test_bwa_stage_emu import FUZZ, _literal_depth_loop, _read_cases, emu, fuzz_summary  # noqa: F401 -- (emu: the module fixture that builds the harness)
+from test_bwa_stage_emu import (FUZZ, LONG_FALLBACK, LONG_LENGTHS, LONG_SEED, _literal_depth_loop, _read_cases, check_long_summary, emu, fuzz_summary,  # noqa: F401 -- (emu: the module
+                                long_summary, read_long_cases)                                                                            # fixture that builds the harness)
 from test_gpu_parity import _compare
 
 pytestmark = pytest.mark.gpu
@@ -125,6 +127,30 @@ def test_depth_kernels_against_the_host_loop_on_the_fuzz_tables(emu, built, tmp_
     assert 4 * held >= blocks and fallbacks > 0
 
 
+def test_depth_kernels_on_long_tables(emu, built, tmp_path):
+    """the tables of tools/bwa_stage_emu.cpp --fuzz-long (Reads lists of one and two rounds of depth_prefix, one block short and one block beyond;
+    what must cross a round only the carry brings) through sq_debug_bwa_depth: route 1, the kernels, against route 0, the host loop, against the
+    literal loop of the reference -- every Support and sum, the fallback flag on the one table whose chromosomes go down (at the first block of
+    the second round), and per table the held blocks the emulated run counted"""
+    out = subprocess.run([str(emu), "--fuzz-long", LONG_SEED, "--write", str(tmp_path / "long.txt")], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout[-2000:]
+    want, per_case = long_summary(out.stdout)
+    check_long_summary(want, per_case)
+    cases = read_long_cases(tmp_path / "long.txt")
+    assert [len(r) for _, r in cases] == LONG_LENGTHS
+    with squid_amd.Context() as ctx:
+        for k, (nodes, reads) in enumerate(cases):
+            assert len(reads) <= 131073 and bool((np.diff(reads[:, 0]) >= 0).all()) == (k != LONG_FALLBACK), k
+            r1 = ctx.debug_bwa_depth(nodes, reads, route=1)
+            r0 = ctx.debug_bwa_depth(nodes, reads, route=0)
+            assert r1["fallback"] == int(k == LONG_FALLBACK) == per_case[k][4], k
+            assert (r0["support"], r0["sums"]) == _literal_depth_loop(nodes.tolist(), reads.tolist()), k
+            if k == LONG_FALLBACK:
+                continue
+            assert (r1["support"], r1["sums"]) == (r0["support"], r0["sums"]), k
+            assert (len(nodes), len(reads), r1["held"], sum(r1["support"])) == per_case[k][:4], k
+
+
 # ---- a hand-made BAM: two contigs, a discordant cluster between them (node boundaries, an edge, breakpoints), a spliced read in front of five
 # unspliced ones, and one record failing each factor of the two filters
 A, B_ = 0, 1
@@ -206,12 +232,23 @@ def test_hand_made_bam(built, tmp_path, monkeypatch):
         assert [n[:5] for n in g1] == [n[:5] for n in nodes]
 
 
-def test_cursor_probes(built, synth, monkeypatch):
+# the second case: seed 12 of the random --bwa shapes, MAPQ spread over 1..40 at -mq 30 -- two thirds of the records that feed Reads are in the
+# table and are not counted at a breakpoint
+PROBE_SEED = 12
+
+
+@pytest.mark.parametrize("case", ["C2", "shape12"])
+def test_cursor_probes(built, synth, monkeypatch, case):
     """sq_debug_bp_support on a --bwa context of the device route: a few hundred breakpoints, runs of adjacent positions inside covered exons
     included (the cursor moves one entry per record, so it lags behind them) -- the kernels over the table against the host loop over the batch"""
     monkeypatch.delenv("SQUID_BWA_STAGES_GPU", raising=False)
-    pre = synth("C2", "--bwa")
-    with squid_amd.Context(star_mapq=False, min_mapqual=1) as ctx:
+    if case == "C2":
+        pre, mq = synth("C2", "--bwa"), 1
+    else:
+        gen, _, params = shapes.draw_bwa(PROBE_SEED)
+        assert case == f"shape{PROBE_SEED}" and shapes.mapq_range(gen) == (1, 40) and params["min_mapqual"] == 30
+        pre, mq = synth("T2", *gen), 30
+    with squid_amd.Context(star_mapq=False, min_mapqual=mq) as ctx:
         ctx.load_bwa(f"{pre}.bam")
         ctx.bwa_on_device()
         ctx.build_graph()

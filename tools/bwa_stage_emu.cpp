@@ -6,6 +6,8 @@
 //   bwa_stage_emu <bwa.bam> [min_mapqual]                       BuildNode_BWA / RawEdges by the library's host code, then both routes
 //   bwa_stage_emu --fuzz <cases> <seed> [--write <file>]        random tables (see make_case); --write keeps the cases as numbers for
 //                                                               the device test (sq_debug_bwa_depth)
+//   bwa_stage_emu --fuzz-long <seed> [--write <file>]           the tables of LONG_SPECS: Reads lists around one and two rounds of depth_prefix
+//                                                               (64 tiles = 65 536 blocks), which the tables of --fuzz (five tiles) never reach
 #include "../squid_amd/csrc/sq_internal.h"
 #include "../squid_amd/csrc/sq_bwa_stage.inc"
 #include <cstdio>
@@ -93,14 +95,18 @@ struct Case {
     bool one_per_chr = false, tiny = false, single = false, empty_chr = false, far_tile = false, dead_tail = false, decreasing = false;
     long exact_end = 0, one_beyond = 0, one_before = 0;
 };
-Case make_case(std::mt19937_64& rng, int index) {
+// what make_table is asked for.  style: 0 random tiling, 1 one node per chromosome, 2 nodes of 1-4 bases, 3 short nodes under dense blocks, 4 one
+// node takes every block.  far_tile: the last block of tile `far_at` stands near the chromosome's end and the two tiles behind it lie in front of it.
+// dead_tail: block `plant_at` (-1: the middle one) lies beyond the last node of its chromosome.  decreasing: block `plant_at` (-1: one of the
+// last 40) lies on the first chromosome, behind a block of a later one.  scale: the chromosomes' lengths times this.
+// few_introns (the long tables): two records in a thousand are spliced, their introns a tenth as long, and no block behind an intron lies beyond the
+// chromosome -- with the rates of the short tables a list of 65 536 blocks has a block that nothing consumes near its start and counts nothing behind it
+struct Spec { int want, style; bool far_tile, dead_tail, decreasing; long far_at, plant_at; int scale; bool few_introns; };
+Case make_table(std::mt19937_64& rng, const Spec& sp) {
     Case cs;
     auto rnd = [&](int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); };
-    const int want = LENGTHS[index % (int)(sizeof LENGTHS / sizeof *LENGTHS)];
-    cs.far_tile = want >= 3300 && index % 3 == 0;
-    const int style = cs.far_tile ? (index % 2 ? 3 : 0) : (index / 2) % 5;  // 0 random tiling, 1 one node per chromosome, 2 nodes of 1-4 bases, 3 short nodes under dense blocks, 4 one node takes every block
-    cs.dead_tail = !cs.far_tile && want >= 63 && index % 4 == 1;
-    cs.decreasing = !cs.far_tile && !cs.dead_tail && want >= 2 && index % 7 == 2;
+    const int want = sp.want, style = sp.style;
+    cs.far_tile = sp.far_tile; cs.dead_tail = sp.dead_tail; cs.decreasing = sp.decreasing;
     const int nchr = cs.far_tile || style == 4 ? 2 : rnd(3, 5);
     const int skip = nchr >= 3 ? rnd(1, nchr - 2) : -1;  // a chromosome between two used ones that no block lies on
     cs.empty_chr = skip >= 0 && want >= 2;
@@ -108,7 +114,7 @@ Case make_case(std::mt19937_64& rng, int index) {
     cs.n_ref = nchr;
     std::vector<std::vector<int>> first((size_t)nchr);  // node index range per chromosome
     for (int ch = 0; ch < nchr; ++ch) {
-        const int L = style == 2 ? rnd(300, 700) : style == 3 ? rnd(1500, 2500) : rnd(3000, 9000);
+        const int L = sp.scale * (style == 2 ? rnd(300, 700) : style == 3 ? rnd(1500, 2500) : rnd(3000, 9000));
         int p = 0;
         while (p < L) {
             int len;
@@ -145,9 +151,14 @@ Case make_case(std::mt19937_64& rng, int index) {
             else { p = rnd(0, L - 1); len = rnd(1, 80); }                                                       // anywhere, over the end included
             r.pos = p;
             r.blk.push_back(std::make_pair(p, len));
-            const int extra = rnd(0, 99) < (style == 3 ? 1 : 2) ? rnd(1, 2) : 0;
+            const int extra = (sp.few_introns ? rnd(0, 999) < 2 : rnd(0, 99) < (style == 3 ? 1 : 2)) ? rnd(1, 2) : 0;
             int at = p + len;
-            for (int k = 0; k < extra && blocks + (int)r.blk.size() < share; ++k) { at += rnd(L / 40, L / 10); const int l2 = rnd(5, 60); r.blk.push_back(std::make_pair(at, l2)); at += l2; }  // (may lie behind the last node)
+            for (int k = 0; k < extra && blocks + (int)r.blk.size() < share; ++k) {
+                at += sp.few_introns ? rnd(L / 400, L / 100) : rnd(L / 40, L / 10);
+                const int l2 = rnd(5, 60);
+                if (sp.few_introns && at + l2 > L) break;
+                r.blk.push_back(std::make_pair(at, l2)); at += l2;  // (may lie behind the last node)
+            }
             blocks += (int)r.blk.size();
             recs.push_back(r);
         }
@@ -156,26 +167,54 @@ Case make_case(std::mt19937_64& rng, int index) {
         made += blocks;
     }
     const size_t nr = cs.reads3.size() / 3;
-    if (cs.far_tile) {  // the last block of the first tile stands near the chromosome's end; the blocks of the next tiles lie in front of it
-        if (nr < 3 * (size_t)bws::TILE_BLOCKS) cs.far_tile = false;
+    if (cs.far_tile) {  // the last block of tile far_at stands near the chromosome's end; the blocks of the next tiles (and those in front) lie in front of it
+        const size_t upto = ((size_t)sp.far_at + 3) * (size_t)bws::TILE_BLOCKS;
+        if (nr < upto) cs.far_tile = false;
         else {
-            // (the later blocks of spliced records are pulled in so that nothing in the three tiles reaches the far block's node)
+            // (the later blocks of spliced records are pulled in so that nothing up to there reaches the far block's node)
             const int L = cs.ref_len[0], far = L - 2;
-            for (size_t j = 0; j < 3 * (size_t)bws::TILE_BLOCKS; ++j) if (cs.reads3[3 * j + 1] >= L * 3 / 5) cs.reads3[3 * j + 1] = rnd(L / 5, L * 3 / 5 - 1);
-            const size_t j = (size_t)bws::TILE_BLOCKS - 1;
+            for (size_t j = 0; j < upto; ++j) if (cs.reads3[3 * j + 1] >= L * 3 / 5) cs.reads3[3 * j + 1] = rnd(L / 5, L * 3 / 5 - 1);
+            const size_t j = ((size_t)sp.far_at + 1) * (size_t)bws::TILE_BLOCKS - 1;
             cs.reads3[3 * j] = 0; cs.reads3[3 * j + 1] = far; cs.reads3[3 * j + 2] = 1;
         }
     }
     if (cs.dead_tail && nr >= 8) {  // a block beyond the last node of its chromosome, in the middle of the list
-        const size_t j = nr / 2;
+        const size_t j = sp.plant_at < 0 ? nr / 2 : (size_t)sp.plant_at;
         cs.reads3[3 * j + 1] = cs.ref_len[(size_t)cs.reads3[3 * j]] + rnd(0, 50);
     } else cs.dead_tail = false;
     if (cs.decreasing && nr >= 2 && cs.reads3[0] != cs.reads3[3 * (nr - 1)]) {  // a block of the first chromosome behind a block of a later one
-        const size_t j = nr - 1 - (size_t)rnd(0, (int)std::min<size_t>(nr / 3, 40));
+        const size_t j = sp.plant_at >= 0 ? (size_t)sp.plant_at : nr - 1 - (size_t)rnd(0, (int)std::min<size_t>(nr / 3, 40));
         if (j >= 1 && cs.reads3[3 * (j - 1)] != cs.reads3[0]) { cs.reads3[3 * j] = cs.reads3[0]; cs.reads3[3 * j + 1] = rnd(0, cs.ref_len[(size_t)cs.reads3[0]] - 1); } else cs.decreasing = false;
     } else cs.decreasing = false;
     return cs;
 }
+Case make_case(std::mt19937_64& rng, int index) {
+    Spec sp;
+    sp.want = LENGTHS[index % (int)(sizeof LENGTHS / sizeof *LENGTHS)];
+    sp.far_tile = sp.want >= 3300 && index % 3 == 0;
+    sp.style = sp.far_tile ? (index % 2 ? 3 : 0) : (index / 2) % 5;
+    sp.dead_tail = !sp.far_tile && sp.want >= 63 && index % 4 == 1;
+    sp.decreasing = !sp.far_tile && !sp.dead_tail && sp.want >= 2 && index % 7 == 2;
+    sp.far_at = 0; sp.plant_at = -1; sp.scale = 1; sp.few_introns = false;
+    return make_table(rng, sp);
+}
+// ---- the long tables.  depth_prefix walks the tiles in rounds of 64 (ROUND blocks) and carries the two running maxima from round to round:
+// lists one block short of a round, exactly one and two rounds, and one block into the second and the third round; random tiling and short
+// nodes under dense blocks.  The specials put the value that must cross a round where only the carry brings it: a far block as the last block of
+// the first round that holds the first two tiles of the second, a block beyond the last node (g = n_nodes: nothing behind it is counted) in the
+// last tile of the first round, and one inside the second round of a list that reaches into the third; and for the other maximum a block of the
+// first chromosome as the only block of the second round, behind a round of later chromosomes (the flag that sends the case to the host loop)
+constexpr long ROUND = 64l * bws::TILE_BLOCKS;
+const Spec LONG_SPECS[] = {
+    {(int)ROUND - 1, 0, false, false, false, 0, -1, 20, true},
+    {(int)ROUND, 3, false, false, false, 0, -1, 20, true},
+    {(int)ROUND + 1, 0, false, false, false, 0, -1, 20, true},
+    {2 * (int)ROUND, 3, true, false, false, 63, -1, 20, true},
+    {2 * (int)ROUND + 1, 0, false, true, false, 0, ROUND + 10 * bws::TILE_BLOCKS + 5, 20, true},
+    {2 * (int)ROUND, 0, false, true, false, 0, ROUND - 500, 20, true},
+    {(int)ROUND + 1, 3, false, false, false, 0, -1, 20, true},
+    {(int)ROUND + 1, 0, false, false, true, 0, ROUND, 20, true},
+};
 void write_case(std::FILE* f, const Case& cs) {
     std::fprintf(f, "case %zu %zu\n", cs.nodes3.size() / 3, cs.reads3.size() / 3);
     for (size_t i = 0; i < cs.nodes3.size(); i += 3) std::fprintf(f, "%d %d %d\n", cs.nodes3[i], cs.nodes3[i + 1], cs.nodes3[i + 2]);
@@ -208,7 +247,55 @@ long compare_depth(const std::vector<int32_t>& nodes3, int n_ref, const std::vec
 }  // namespace
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: bwa_stage_emu <bwa.bam> [min_mapqual] | --fuzz <cases> <seed> [--write <file>]\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: bwa_stage_emu <bwa.bam> [min_mapqual] | --fuzz <cases> <seed> [--write <file>] | --fuzz-long <seed> [--write <file>]\n"); return 2; }
+    if (!std::strcmp(argv[1], "--fuzz-long")) {
+        if (argc < 3) return 2;
+        std::mt19937_64 rng((uint64_t)std::strtoull(argv[2], nullptr, 10));
+        std::FILE* out = argc > 4 && !std::strcmp(argv[3], "--write") ? std::fopen(argv[4], "w") : nullptr;
+        const int cases = (int)(sizeof LONG_SPECS / sizeof *LONG_SPECS);
+        long bad = 0, blocks = 0, held = 0, counted = 0;
+        int far_round = 0, dead_round = 0, dead_second = 0, random_tiling = 0, dense = 0, down_round = 0;
+        for (int k = 0; k < cases; ++k) {
+            const Spec& sp = LONG_SPECS[k];
+            Case cs = make_table(rng, sp);
+            if (out) write_case(out, cs);
+            const size_t nr = cs.reads3.size() / 3, T = (size_t)bws::TILE_BLOCKS;
+            const int nn = (int)(cs.nodes3.size() / 3);
+            const Plain pl = plain_held(cs.nodes3, cs.reads3);
+            long b = 0, h = 0, cn = 0;
+            if ((long)nr != sp.want) { ++b; std::printf("   case %d: %zu blocks, asked for %d\n", k, nr, sp.want); }
+            if (pl.decreasing != sp.decreasing || cs.decreasing != sp.decreasing) { ++b; std::printf("   case %d: the chromosome order along Reads is not what was asked for\n", k); }
+            b += compare_depth(cs.nodes3, cs.n_ref, cs.ref_len, k % 2 == 1, cs.reads3, sp.decreasing, h, cn, true);
+            // what the specials promise, checked on the tables themselves
+            if (sp.decreasing) {  // the first block whose chromosome is smaller than one in front of it is the first block of a round, and its tile holds nothing else
+                size_t first = 1;
+                for (int cmax = cs.reads3[0]; first < nr && cs.reads3[3 * first] >= cmax; ++first) cmax = cs.reads3[3 * first];
+                if (first == (size_t)sp.plant_at && first % (size_t)ROUND == 0 && first + 1 == nr) ++down_round; else { ++b; std::printf("   case %d: no chromosome going down at the first block of a round (first %zu)\n", k, first); }
+            }
+            if (sp.far_tile) {  // the last block of the first round holds every block of the first two tiles of the second
+                const size_t far = ((size_t)sp.far_at + 1) * T - 1;
+                bool ok = cs.far_tile && (long)far == ROUND - 1;
+                for (size_t j = far + 1; ok && j <= far + 2 * T; ++j) ok = pl.m[j] != pl.g[j] && pl.m[j] == pl.g[far] && pl.m[j] < nn;
+                if (ok) ++far_round; else { ++b; std::printf("   case %d: the far block does not hold two tiles of the second round\n", k); }
+            }
+            if (sp.dead_tail) {  // the first block nothing consumes is the planted one, with counted blocks in front of it and blocks of a later round behind it
+                size_t first = 0;
+                while (first < nr && pl.m[first] != nn) ++first;
+                const bool ok = cs.dead_tail && first == (size_t)sp.plant_at && cn > 0 && first / (size_t)ROUND < (nr - 1) / (size_t)ROUND;
+                if (ok) { ++dead_round; dead_second += first / (size_t)ROUND == 1; } else { ++b; std::printf("   case %d: no block beyond the last node in front of a later round (first %zu)\n", k, first); }
+            }
+            random_tiling += sp.style == 0; dense += sp.style == 3;
+            if (b) std::printf("case %d: %ld differences\n", k, b);
+            bad += b; blocks += (long)nr; held += h; counted += cn;  // (a fallback case adds its blocks and nothing else)
+            std::printf("long case %d: %zu nodes, %zu blocks, held %ld, counted %ld, fallback %d\n", k, (size_t)nn, nr, h, cn, (int)sp.decreasing);
+        }
+        if (out) std::fclose(out);
+        std::printf("%d long cases, %ld blocks, held %ld, counted %ld, random tiling %d, short nodes under dense blocks %d, far block holds two tiles of the next round %d, "
+                    "block beyond the last node in front of a later round %d (inside the second round %d), chromosome going down at the first block of a round %d\n",
+                    cases, blocks, held, counted, random_tiling, dense, far_round, dead_round, dead_second, down_round);
+        std::printf(bad ? "%ld DIFFERENT\n" : "%ld differences: same\n", bad);
+        return bad ? 1 : 0;
+    }
     if (!std::strcmp(argv[1], "--fuzz")) {
         if (argc < 4) return 2;
         const int cases = std::atoi(argv[2]);
@@ -272,7 +359,7 @@ int main(int argc, char** argv) {
     const bws::Recs R{(int64_t)nrec, hb.refid.data(), hb.pos.data(), hb.mrefid.data(), hb.mpos.data(), hb.flag.data(), hb.mapq.data(), hb.aux.data(), hb.blk_off.data()};
     std::vector<uint8_t> cls(nrec + 1, 0xff);
     std::vector<int32_t> blk_chr(nblk + 1, -2);
-    long bad = 0, n_reads = 0, n_p3 = 0, n_named = 0;
+    long bad = 0, n_reads = 0, n_p3 = 0, n_named = 0, n_left = 0, n_below = 0;
     for (int64_t r = (int64_t)nrec; r-- > 0;) bws::classify(R, c.P.min_mapqual, nullptr, cls.data(), blk_chr.data(), r);
     for (size_t r = 0; r < nrec; ++r) {
         if (((cls[r] & bws::CLS_READS) != 0) != (h_reads[r] != 0)) { if (bad < 10) std::printf("   record %zu: READS bit %d, host %d\n", r, (cls[r] & bws::CLS_READS) != 0, (int)h_reads[r]); ++bad; }
@@ -283,6 +370,10 @@ int main(int argc, char** argv) {
         const bool reads = (cls[r] & bws::CLS_READS) != 0, p3 = (cls[r] & bws::CLS_P3) != 0;
         if (reads != (h_reads[r] != 0) || p3 != (h_look[r] != 0) || (cls[r] & ~(bws::CLS_READS | bws::CLS_P3))) { if (bad < 10) std::printf("   record %zu: class %d, host READS %d / look %d\n", r, (int)cls[r], (int)h_reads[r], (int)h_look[r]); ++bad; }
         n_reads += reads; n_p3 += p3; n_named += h_names[r];
+        // of the host's READS records: the middle class (MAPQ below -mq: feeds Reads, not looked at by the breakpoint support), and the left-hand
+        // records of a pair among the others
+        if (h_reads[r] && hb.mapq[r] < c.P.min_mapqual) ++n_below;
+        else if (h_reads[r] && !(hb.flag[r] & 0x8) && hb.mrefid[r] == hb.refid[r] && (hb.mpos[r] > hb.pos[r] || (hb.mpos[r] == hb.pos[r] && (hb.flag[r] & 0x80)))) ++n_left;
     }
     // the depth kernels over the block arrays against the nodes of the host loop, and against the loop on the flat Reads list
     std::vector<int32_t> nodes3, reads3;
@@ -305,8 +396,9 @@ int main(int argc, char** argv) {
     }
     const Plain pl = plain_held(nodes3, reads3);
     if (pl.held != d.held) { std::printf("   held blocks: %ld by the definition, %ld emulated\n", pl.held, d.held); ++bad; }
-    std::printf("%zu records, %zu blocks, READS records %ld (%zu blocks in Reads), breakpoint-support records %ld, records named like a rebuilt fragment %ld of %zu names, %zu nodes, held blocks %ld\n",
-                nrec, nblk, n_reads, reads3.size() / 3, n_p3, n_named, c.chim_names.size(), c.nodes.size(), d.held);
+    std::printf("%zu records, %zu blocks, READS records %ld (%zu blocks in Reads), breakpoint-support records %ld, records named like a rebuilt fragment %ld of %zu names, %zu nodes, held blocks %ld, "
+                "left-hand READS records %ld, READS records below -mq %d: %ld\n",
+                nrec, nblk, n_reads, reads3.size() / 3, n_p3, n_named, c.chim_names.size(), c.nodes.size(), d.held, n_left, c.P.min_mapqual, n_below);
     std::printf(bad ? "%ld DIFFERENT\n" : "%ld differences: same\n", bad);
     return bad ? 1 : 0;
 }
