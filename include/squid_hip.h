@@ -182,6 +182,18 @@ int sq_chimeric_on_device(sq_ctx* c, int32_t on);
  * bwa_depth_held_blocks: the blocks the cursor holds in front of a later node, ledger W6; bwa_reads_records / bwa_bp_records: the records the
  * two loops look at, on either route).  sq_save_records refuses a context whose resident table is a --bwa batch. */
 int sq_bwa_on_device(sq_ctx* c, int32_t on);
+/* on != 0: a --bwa context also runs the BAM loop of RawEdges (src/SegmentGraph.cpp:1712-1880) as kernels over the resident record table
+ * (squid_amd/csrc/sq_bwa_edges.inc): a fragment table made from the records, the position LocateRead carries from record to record solved
+ * exactly by the position chain of the chimeric device stages, the edges summed in a (key, count) table, and the three lists of the loop
+ * (PartialAlign, FirstDisInserted, the multi-aligned second mates) compacted in record order.  The host keeps what needs QNAMEs: the name
+ * sort, the merged and rebuilt fragments, the -1 edges.  It implies the resident table: a context with it on behaves as if sq_bwa_on_device
+ * were on as well.  Every result is identical to the host route's.  Default: off.  Accepted on any context; only a --bwa context looks at it.
+ * SQUID_BWA_EDGES_GPU=1 / =0 in the environment of sq_create forces / forbids the route whatever this call says.  A graph whose table is not
+ * resident, a record with two aligned blocks at one read offset, an input on which the reference would assert (a block behind the last node,
+ * an edge that leaves the node table) and a device buffer that cannot be had take the host loop for that graph, with the host loop's results
+ * and error text (sq_get_timing: bwa_edges_device_fallback counts these; bwa_edge_soft_fragments: the records whose first block had to be
+ * resolved in record order; bwa_edge_lists: the entries of the three lists; host_bwa_raw_edges_tail: the host's part). */
+int sq_bwa_edges_on_device(sq_ctx* c, int32_t on);
 
 /* vector<vector<int>> Ordering() -- src/SegmentGraph.cpp:3236-3262: CSR of signed 1-based node ids */
 typedef struct sq_orders {
@@ -339,6 +351,28 @@ int sq_debug_chim_stages(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n
  * MatchRef (AvgDepth = 1.0 * sum / Length); out2 = {blocks the cursor held in front of a later node than their own (route 1), 1 when the
  * kernels saw a chromosome go down along Reads and returned nothing -- the library then takes the host loop (route 1)}. */
 int sq_debug_bwa_depth(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, int32_t* support, int32_t* sums, int64_t* out2);
+/* tests: the BAM loop of RawEdges alone.  sq_debug_bwa_raw_edges: over the batch of a --bwa context, behind sq_build_graph, on the nodes of
+ * stage 1 (sq_graph_view).  sq_debug_bwa_raw_edges_tables: over caller-supplied tables -- nodes3: n_nodes x {chr, pos, len} tiling every
+ * chromosome; rec8: n_rec x {RefID, Position, MateRefID, MatePosition, flag, TotalLen, MapQuality, SQ_AUX_* bits}; blk_off: n_rec + 1;
+ * blk4: the aligned blocks x {RefPos, MatchRef, ReadPos, MatchRead} -- which take the place of the context's resident table (the next graph
+ * of a --bwa context uploads its batch again).  route 0: the host loop in one go; route 1: the kernels of sq_bwa_edges_on_device.  The result
+ * stays valid until the next call on the same thread: the summed (key, weight) list sorted by key (key = ind1 << 32 | ind2 << 2 | head1 << 1
+ * | head2), the three lists as record indices in record order, the would-be edges of the listed second mates, the position LocateRead is
+ * left at, the number of edges the loop emitted; route 1: the soft fragments and 1 when the kernels handed the graph back to the host loop
+ * (nothing else is then valid).  Route 0 fails with SQ_E_ASSERT where the library's host loop does. */
+typedef struct sq_bwa_edges_debug {
+    int64_t n_edges;
+    const uint64_t* keys;
+    const int32_t* weights;
+    int64_t n_part, n_first_dis, n_second;
+    const uint32_t *part, *first_dis, *second;
+    const uint64_t* second_keys; /* n_second */
+    int64_t n_emitted, n_soft;
+    int32_t final_pos, fallback;
+} sq_bwa_edges_debug;
+int sq_debug_bwa_raw_edges(sq_ctx* c, int32_t route, sq_bwa_edges_debug* out);
+int sq_debug_bwa_raw_edges_tables(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4,
+                                  sq_bwa_edges_debug* out);
 /* tuning: the two BGZF inflate kernels on the first max_blocks blocks of a file, each ALONE on the device, timed with HIP events (the
  * reader overlaps them with everything else).  variant: 2 = the lane-per-block token pass (k_inflate_tok2), else CH * 100 + PB of the
  * wave-per-block pass (k_inflate_spec: 51211, 51210, 25610, 25611, 38411, 102411).  check != 0 compares every block with zlib.

@@ -26,6 +26,7 @@ EXPORTS = [
     "sq_total_order", "sq_set_allgather", "sq_rccl_unique_id", "sq_rccl_init", "sq_rccl_attach", "sq_exchange", "sq_exchange_stats",
     "sq_rccl_available", "sq_rccl_release", "sq_debug_rccl_selftest", "sq_debug_token_bench", "sq_ingest_bwa_file", "sq_junction_sequences", "sq_release_reader_buffers", "sq_keep_host_memory", "sq_keep_stage_graphs",
     "sq_chimeric_on_device", "sq_debug_chim_stages", "sq_bwa_on_device", "sq_debug_bwa_depth",
+    "sq_bwa_edges_on_device", "sq_debug_bwa_raw_edges", "sq_debug_bwa_raw_edges_tables",
 ]
 
 
@@ -75,6 +76,12 @@ class SqCounts(C.Structure):
                                           "n_kept_p2", "n_raw_edges", "n_unique_edges", "n_order_unsolved", "token_passes_side_by_side", "replay_candidates_checked", "replay_count_mismatches", "chimeric_through_gpu_reader")]
 
 
+class SqBwaEdgesDebug(C.Structure):
+    _fields_ = [("n_edges", C.c_int64), ("keys", C.POINTER(C.c_uint64)), ("weights", _P32), ("n_part", C.c_int64), ("n_first_dis", C.c_int64), ("n_second", C.c_int64),
+                ("part", C.POINTER(C.c_uint32)), ("first_dis", C.POINTER(C.c_uint32)), ("second", C.POINTER(C.c_uint32)), ("second_keys", C.POINTER(C.c_uint64)),
+                ("n_emitted", C.c_int64), ("n_soft", C.c_int64), ("final_pos", C.c_int32), ("fallback", C.c_int32)]
+
+
 class SquidError(RuntimeError):
     pass
 
@@ -112,6 +119,9 @@ def load_library() -> C.CDLL:
         lib.sq_debug_chim_stages.argtypes = [C.c_void_p, C.c_int32, _P32, C.c_int32, _P32, C.c_int32, _P32, _P32, _P32, _P32, C.c_int32, _P32, C.POINTER(C.c_int64)]
         lib.sq_bwa_on_device.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_debug_bwa_depth.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _P32, C.c_int64, _P32, _P32, _P32, C.POINTER(C.c_int64)]
+        lib.sq_bwa_edges_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_debug_bwa_raw_edges.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqBwaEdgesDebug)]
+        lib.sq_debug_bwa_raw_edges_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _P32, C.c_int64, _P32, C.POINTER(C.c_uint32), _P32, C.POINTER(SqBwaEdgesDebug)]
         lib.sq_clear_records.argtypes = [C.c_void_p]
         lib.sq_release_reader_buffers.argtypes = [C.c_void_p]
         lib.sq_set_source.argtypes = [C.c_void_p, C.c_char_p]
@@ -257,6 +267,46 @@ class Context:
         """sq_bwa_on_device: a --bwa context keeps its batch in HBM as well and the next build_graph / call_sv compute the node depth and the
         breakpoint support there (same results; off by default; any other context ignores it)"""
         self._chk(self.lib.sq_bwa_on_device(self.h, 1 if on else 0), "sq_bwa_on_device")
+
+    def bwa_edges_on_device(self, on: bool = True):
+        """sq_bwa_edges_on_device: a --bwa context also runs the record loop of RawEdges over its batch in HBM (it implies bwa_on_device; same
+        results; off by default; any other context ignores it)"""
+        self._chk(self.lib.sq_bwa_edges_on_device(self.h, 1 if on else 0), "sq_bwa_edges_on_device")
+
+    @staticmethod
+    def _bwa_edges_result(d) -> dict:
+        import numpy as np
+
+        def arr(ptr, cnt):
+            return np.ctypeslib.as_array(ptr, shape=(cnt,)).tolist() if cnt else []
+
+        return {"keys": arr(d.keys, d.n_edges), "weights": arr(d.weights, d.n_edges), "part": arr(d.part, d.n_part), "first_dis": arr(d.first_dis, d.n_first_dis),
+                "second": arr(d.second, d.n_second), "second_keys": arr(d.second_keys, d.n_second), "final_pos": int(d.final_pos), "n_emitted": int(d.n_emitted),
+                "n_soft": int(d.n_soft), "fallback": int(d.fallback)}
+
+    def debug_bwa_raw_edges(self, route: int = 1) -> dict:
+        """sq_debug_bwa_raw_edges (tests), behind build_graph on a --bwa context: the record loop of RawEdges alone, route 0 = the host loop in one
+        go, 1 = the kernels over the resident table.  keys / weights: the summed edges sorted by key; part / first_dis / second: record indices in
+        record order; second_keys; final_pos; n_emitted; route 1: n_soft and fallback (1: nothing else is valid)"""
+        d = SqBwaEdgesDebug()
+        self._chk(self.lib.sq_debug_bwa_raw_edges(self.h, route, C.byref(d)), "sq_debug_bwa_raw_edges")
+        return self._bwa_edges_result(d)
+
+    def debug_bwa_raw_edges_tables(self, nodes, records, blk_off, blocks, route: int = 1) -> dict:
+        """sq_debug_bwa_raw_edges_tables (tests): the same on the given tables.  nodes: [(chr, pos, len)]; records: [(refid, pos, mate refid, mate pos,
+        flag, totlen, mapq, aux)]; blk_off: len(records) + 1 block offsets; blocks: [(refpos, matchref, readpos, matchread)].  The tables take the
+        place of the context's resident table."""
+        import numpy as np
+
+        nd = np.ascontiguousarray(np.asarray(nodes, dtype=np.int32).reshape(-1, 3))
+        rc_ = np.ascontiguousarray(np.asarray(records, dtype=np.int32).reshape(-1, 8))
+        bo = np.ascontiguousarray(np.asarray(blk_off, dtype=np.uint32))
+        bl = np.ascontiguousarray(np.asarray(blocks, dtype=np.int32).reshape(-1, 4))
+        assert len(bo) == len(rc_) + 1 and int(bo[-1]) == len(bl)
+        d = SqBwaEdgesDebug()
+        self._chk(self.lib.sq_debug_bwa_raw_edges_tables(self.h, route, len(nd), nd.ctypes.data_as(_P32), len(rc_), rc_.ctypes.data_as(_P32), bo.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                         bl.ctypes.data_as(_P32), C.byref(d)), "sq_debug_bwa_raw_edges_tables")
+        return self._bwa_edges_result(d)
 
     def debug_bwa_depth(self, nodes, reads, route: int = 1) -> dict:
         """sq_debug_bwa_depth (tests): the node depth loop of BuildNode_BWA on the given tables, route 0 = the host loop, 1 = the kernels.

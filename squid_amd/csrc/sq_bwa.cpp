@@ -417,45 +417,63 @@ static int bwa_home_node(const std::vector<Node>& N, int start, const Blk& b) { 
 }
 
 // ---- RawEdges (:1698-1930): the edges of the BAM loop, the -1 edges of multi-aligned second mates, the fragments rebuilt from the
-// partially aligned reads and their split edges
-static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw) {
-    const std::vector<Node>& N = c->nodes;
+// partially aligned reads and their split edges.  Two halves that both routes share: the BAM loop (bwa_raw_edges_loop on the host,
+// dev_bwa_raw_edges on the device: sq_bwa_edges.inc) and everything behind it (bwa_raw_edges_tail), with prepare / finish_prepare --
+// the fragment of one record -- in front of both.
+namespace {
+// the fragment of record ri as the loop builds it up to its LocateRead call: 0 = the record is skipped or locates nothing,
+// 1 = first mate (:1745-1806), 2 = multi-aligned second mate (:1807-1860); `part`: it also goes to PartialAlign
+int prepare(const HostBatch& hb, size_t ri, Frag& f, bool& part) {
+    const RecRef r{hb, ri};
+    part = false;
+    if (r.dup() || !r.mapped()) return 0;
+    if (r.first() ? (r.multi() || hb.mapq[ri] == 0) : !r.multi()) return 0;  // :1723-1726 (W5)
+    BlkList& own = r.first() ? f.a : f.b;  // (f.name: given by the caller where a list keeps it -- two std::strings per record otherwise, most of this loop's time)
+    for (size_t k = 0; k < r.nblk(); ++k) own.push_back(r.blk(k));
+    std::sort(own.begin(), own.end(), blk_less_readpos);
+    (r.first() ? f.atot : f.btot) = r.totlen();
+    (r.first() ? f.alow : f.blow) = r.lowphred();
+    part = !r.multi() && (clipped_end(f.a, f.atot, f.alow) || clipped_end(f.b, f.btot, f.blow));
+    return r.first() ? ((!f.a.empty() && (f.a.front().readpos <= 15 || f.alow)) ? 1 : 0) : (!f.b.empty() ? 2 : 0);
+}
+// (the mate stub and, for a second mate, the shortened own block: what LocateRead sees -- after the copy for PartialAlign was taken)
+void finish_prepare(const HostBatch& hb, size_t ri, Frag& f, int kind) {
+    const RecRef r{hb, ri};
+    if (r.mate_mapped() && r.mrefid() != -1) (r.first() ? f.b : f.a).push_back(Blk{r.mrefid(), r.mpos(), 0, 15, 15, r.mate_rev(), false});
+    if (kind == 2) { f.b.resize(1); f.b[0].matchref = 15; f.b[0].matchread = 15; }
+}
+void clear_frag(Frag& f) { f.a.clear(); f.b.clear(); f.name.clear(); f.atot = 0; f.btot = 0; f.alow = false; f.blow = false; }
+// what the BAM loop (:1712-1880) leaves behind: the position LocateRead stands at, the edges (summed per key or not: BuildEdges sorts
+// the list and adds the weights of equal keys up, :1943-1957), the -1 edges of the listed second mates, and the three lists -- in record
+// order -- as record indices.  The tail turns them into fragments and names.
+struct LoopResult {
+    int hint = 0;
+    std::vector<Edge> raw, second_edges;
+    std::vector<uint32_t> part, first_dis, second;
+    int64_t n_emitted = 0;  // edges as the loop emitted them
+};
+Edge edge_unpack(unsigned long long key, int w) {
+    Edge e;
+    e.a = (int32_t)(key >> 32); e.b = (int32_t)((key & 0xffffffffull) >> 2); e.ha = (key >> 1) & 1; e.hb = key & 1; e.w = w; e.gw = 0;
+    return e;
+}
+
+// the BAM loop on the host threads.  one_go: one stretch (sq_debug_bwa_raw_edges, tools/bwa_edges_emu.cpp)
+int bwa_raw_edges_loop(sq_ctx* c, const HostBatch& hb, const std::vector<Node>& N, bool one_go, LoopResult& L) {
     const int nn = (int)N.size();
     auto in_range = [&](int i) { return i >= 0 && i < nn; };
     auto discordant = [&](const Edge& e) { return edge_discordant(c, N, e); };
-    // What the BAM loop (:1712-1880) leaves behind, per stretch of records: the loop carries ONE thing from record to record -- the
-    // position LocateRead starts from (`hint`: the node of the last located first block) -- and appends to lists whose order is either
-    // the record order (PartialAlign: sorted by name afterwards with an unstable sort, so the order going in counts) or does not matter
-    // (the edges are sorted and summed, the names of FirstDisInserted are sorted, the -1 edges are looked up one by one).  A stretch can
-    // therefore start behind any record whose first block lies deep inside ONE node -- LocateRead ends there from any start (sq_graph.cpp,
-    // frag_first_block_pins) --, and the stretches are worked on side by side and strung together in order.
+    // The loop carries ONE thing from record to record -- the position LocateRead starts from (`hint`: the node of the last located first
+    // block) -- and appends to lists whose order is either the record order (PartialAlign: sorted by name afterwards with an unstable sort,
+    // so the order going in counts) or does not matter (the edges are sorted and summed, the names of FirstDisInserted are sorted, the -1
+    // edges are looked up one by one).  A stretch can therefore start behind any record whose first block lies deep inside ONE node --
+    // LocateRead ends there from any start (sq_graph.cpp, frag_first_block_pins) --, and the stretches are worked on side by side and strung
+    // together in order.
     struct Piece {
         int hint = 0;
         std::vector<Edge> raw, second_edges;
-        std::vector<Frag> partial;
-        std::vector<std::string> first_dis, second_names;
+        std::vector<uint32_t> part, first_dis, second;
         int rc = SQ_OK; const char* err = nullptr;
-    };
-    // the fragment of record ri as the loop builds it up to its LocateRead call: 0 = the record is skipped or locates nothing,
-    // 1 = first mate (:1745-1806), 2 = multi-aligned second mate (:1807-1860); `part`: it also goes to PartialAlign
-    auto prepare = [&](size_t ri, Frag& f, bool& part) -> int {
-        const RecRef r{hb, ri};
-        part = false;
-        if (r.dup() || !r.mapped()) return 0;
-        if (r.first() ? (r.multi() || hb.mapq[ri] == 0) : !r.multi()) return 0;  // :1723-1726 (W5)
-        BlkList& own = r.first() ? f.a : f.b;  // (f.name: given by the caller where a list keeps it -- two std::strings per record otherwise, most of this loop's time)
-        for (size_t k = 0; k < r.nblk(); ++k) own.push_back(r.blk(k));
-        std::sort(own.begin(), own.end(), blk_less_readpos);
-        (r.first() ? f.atot : f.btot) = r.totlen();
-        (r.first() ? f.alow : f.blow) = r.lowphred();
-        part = !r.multi() && (clipped_end(f.a, f.atot, f.alow) || clipped_end(f.b, f.btot, f.blow));
-        return r.first() ? ((!f.a.empty() && (f.a.front().readpos <= 15 || f.alow)) ? 1 : 0) : (!f.b.empty() ? 2 : 0);
-    };
-    // (the mate stub and, for a second mate, the shortened own block: what LocateRead sees -- after the copy for PartialAlign was taken)
-    auto finish_prepare = [&](size_t ri, Frag& f, int kind) {
-        const RecRef r{hb, ri};
-        if (r.mate_mapped() && r.mrefid() != -1) (r.first() ? f.b : f.a).push_back(Blk{r.mrefid(), r.mpos(), 0, 15, 15, r.mate_rev(), false});
-        if (kind == 2) { f.b.resize(1); f.b[0].matchref = 15; f.b[0].matchread = 15; }
     };
     auto run = [&](size_t lo, size_t hi, Piece& P) {
         std::vector<int> rn;
@@ -474,12 +492,12 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
         };
         Frag f;  // (one object for the stretch, emptied per record: its two block lists keep their storage -- a fresh Frag per record was two or three allocations per record on every thread)
         for (size_t ri = lo; ri < hi; ++ri) {
-            f.a.clear(); f.b.clear(); f.name.clear(); f.atot = 0; f.btot = 0; f.alow = false; f.blow = false;
+            clear_frag(f);
             bool part;
-            const int kind = prepare(ri, f, part);
-            if (part) { f.name = RecRef{hb, ri}.qname(); P.partial.push_back(f); }
+            const int kind = prepare(hb, ri, f, part);
+            if (part) P.part.push_back((uint32_t)ri);  // (the tail builds the fragment again, with its name)
             if (kind == 0) continue;  // (a record that locates nothing leaves nothing else behind: its mate stub is only looked at by LocateRead)
-            finish_prepare(ri, f, kind);
+            finish_prepare(hb, ri, f, kind);
             const size_t na = f.a.size();
             if (kind == 1) {
                 locate_fragment(N, hint, f, rn);
@@ -495,7 +513,7 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
                     const int i = rn[na - 1], j = rn.back();
                     if (i != j && i != -1 && j != -1 && !pair_overlap(f, rn, i, j)) {
                         if (!add(i, f.a.back().rev, j, f.b.back().rev, 1)) return;
-                        if (discordant(P.raw.back())) P.first_dis.push_back(RecRef{hb, ri}.qname());
+                        if (discordant(P.raw.back())) P.first_dis.push_back((uint32_t)ri);
                     }
                 }
             } else {
@@ -509,7 +527,7 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
                     if (i != j && i != -1 && j != -1 && !overlap) {
                         if (!in_range(i) || !in_range(j)) { P.rc = SQ_E_ASSERT; P.err = "an edge would leave the node table (the reference asserts, SegmentGraph.cpp:1852)"; return; }
                         const Edge e = make_edge(i, f.a.back().rev, j, f.b.back().rev, -1);
-                        if (discordant(e)) { P.second_names.push_back(RecRef{hb, ri}.qname()); P.second_edges.push_back(e); }
+                        if (discordant(e)) { P.second.push_back((uint32_t)ri); P.second_edges.push_back(e); }
                     }
                 }
             }
@@ -524,7 +542,7 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
     const int threads = c->pool ? c->pool->size() + 1 : 1;
     std::vector<size_t> cut{0};
     std::vector<int> start{0};
-    if (threads > 1 && (piece_env > 0 || nrec >= 200000)) {
+    if (!one_go && threads > 1 && (piece_env > 0 || nrec >= 200000)) {
         const size_t want = piece_env > 0 ? std::max<size_t>(1, nrec / (size_t)piece_env) : (size_t)(4 * threads);
         for (size_t k = 1; k < want; ++k) {
             const size_t at = nrec * k / want;
@@ -532,9 +550,9 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
             for (size_t q = at; q-- > cut.back() && at - q <= 4096;) {
                 Frag f;
                 bool part;
-                const int kind = prepare(q, f, part);
+                const int kind = prepare(hb, q, f, part);
                 if (kind == 0) continue;
-                finish_prepare(q, f, kind);
+                finish_prepare(hb, q, f, kind);
                 int node = -1;
                 if (frag_first_block_pins(N, f, node)) { cut.push_back(q + 1); start.push_back(node); break; }
             }
@@ -543,7 +561,7 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
     cut.push_back(nrec);
     re_lap("stretches planned");
     const int np = (int)cut.size() - 1;
-    c->timer.add("bwa_raw_edge_stretches", 0.0, 0.0, np);  // (how many stretches the loop ran in: tests)
+    if (!one_go) c->timer.add("bwa_raw_edge_stretches", 0.0, 0.0, np);  // (how many stretches the loop ran in: tests)
     std::vector<Piece> pieces((size_t)np);
     for (int k = 0; k < np; ++k) pieces[(size_t)k].hint = start[(size_t)k];
     // (the edges of a stretch are summed per key before they are strung together -- BuildEdges sorts the list and adds the weights of equal
@@ -558,25 +576,41 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
     };
     if (np > 1) c->pool->parallel_for(np, 1 << 20, [&](int k) { run(cut[(size_t)k], cut[(size_t)k + 1], pieces[(size_t)k]); emitted[(size_t)k] = (int64_t)pieces[(size_t)k].raw.size(); if (!pieces[(size_t)k].rc) presum(pieces[(size_t)k].raw); });
     else { run(0, nrec, pieces[0]); emitted[0] = (int64_t)pieces[0].raw.size(); }
-    int64_t n_emitted = 0;
-    for (int64_t e : emitted) n_emitted += e;
+    L.n_emitted = 0;
+    for (int64_t e : emitted) L.n_emitted += e;
     re_lap("record loop");
-    int hint = 0;
-    std::vector<Frag> partial;
-    std::vector<std::string> first_dis, second_names;
-    std::vector<Edge> second_edges;
-    std::vector<int> rn;
     for (Piece& P : pieces) {
         if (P.rc) return fail(c, P.rc, P.err);  // (the first stretch in record order that ran into one: what the loop in one go would have hit first)
-        raw.insert(raw.end(), P.raw.begin(), P.raw.end());
-        partial.insert(partial.end(), std::make_move_iterator(P.partial.begin()), std::make_move_iterator(P.partial.end()));
-        first_dis.insert(first_dis.end(), std::make_move_iterator(P.first_dis.begin()), std::make_move_iterator(P.first_dis.end()));
-        second_names.insert(second_names.end(), std::make_move_iterator(P.second_names.begin()), std::make_move_iterator(P.second_names.end()));
-        second_edges.insert(second_edges.end(), P.second_edges.begin(), P.second_edges.end());
-        hint = P.hint;
+        L.raw.insert(L.raw.end(), P.raw.begin(), P.raw.end());
+        L.part.insert(L.part.end(), P.part.begin(), P.part.end());
+        L.first_dis.insert(L.first_dis.end(), P.first_dis.begin(), P.first_dis.end());
+        L.second.insert(L.second.end(), P.second.begin(), P.second.end());
+        L.second_edges.insert(L.second_edges.end(), P.second_edges.begin(), P.second_edges.end());
+        L.hint = P.hint;
     }
-    const size_t raw_strung = raw.size();
     re_lap("stretches strung");
+    return SQ_OK;
+}
+
+// everything behind the BAM loop (:1881-1930): the -1 edges whose first mate added a discordant pair edge, the fragments rebuilt from the
+// partially aligned reads, their split edges.  `raw` holds the loop's edges and gets the tail's
+int bwa_raw_edges_tail(sq_ctx* c, const HostBatch& hb, const std::vector<Node>& N, const LoopResult& L, std::vector<Edge>& raw) {
+    const int nn = (int)N.size();
+    auto in_range = [&](int i) { return i >= 0 && i < nn; };
+    const auto t_re0 = std::chrono::steady_clock::now();
+    auto re_lap = [&](const char* what) { if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "RawEdges tail: %-23s at %8.1f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_re0).count()); };
+    int hint = L.hint;
+    std::vector<int> rn;
+    // the listed records again, with their names: PartialAlign's fragments (as prepare leaves them), the names of the two other lists
+    std::vector<Frag> partial(L.part.size());
+    auto build = [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; ++k) { bool part; prepare(hb, L.part[k], partial[k], part); partial[k].name = RecRef{hb, L.part[k]}.qname(); } };
+    if (c->pool && partial.size() > 100000) { const int np = 8 * (c->pool->size() + 1); c->pool->parallel_for(np, 1 << 20, [&](int k) { build(partial.size() * (size_t)k / (size_t)np, partial.size() * ((size_t)k + 1) / (size_t)np); }); }
+    else build(0, partial.size());
+    std::vector<std::string> first_dis, second_names;
+    for (const uint32_t ri : L.first_dis) first_dis.push_back(RecRef{hb, ri}.qname());
+    for (const uint32_t ri : L.second) second_names.push_back(RecRef{hb, ri}.qname());
+    re_lap("fragments and names");
+    const size_t raw_strung = raw.size();
     auto add = [&](int i, bool hi, int j, bool hj, int w) -> int {
         if (!in_range(i) || !in_range(j)) return fail(c, SQ_E_ASSERT, "an edge would leave the node table (the reference asserts, SegmentGraph.cpp:1760)");
         raw.push_back(make_edge(i, hi, j, hj, w));
@@ -591,7 +625,7 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
     };
     std::sort(first_dis.begin(), first_dis.end());
     for (size_t k = 0; k < second_names.size(); ++k)
-        if (std::binary_search(first_dis.begin(), first_dis.end(), second_names[k])) raw.push_back(second_edges[k]);
+        if (std::binary_search(first_dis.begin(), first_dis.end(), second_names[k])) raw.push_back(L.second_edges[k]);
     // the fragments of the partially aligned reads: grouped by name (the sort of :1883 is libstdc++'s introsort on the names, ledger B8),
     // merged, stored untrimmed, located from the hint the loop above left behind (W4); the last group is dropped (W3)
     // (what is sorted is the index of every fragment with the same comparison: introsort takes the same decisions, hence the same order, without
@@ -633,7 +667,74 @@ static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw)
     c->chim_names.erase(std::unique(c->chim_names.begin(), c->chim_names.end()), c->chim_names.end());
     c->counts.n_chim_fragments = (int64_t)rebuilt.size();
     re_lap("fragments rebuilt");
-    c->counts.n_raw_edges = n_emitted + (int64_t)(raw.size() - raw_strung);  // (as the loops emitted them: the stretches' edges arrive summed)
+    c->counts.n_raw_edges = L.n_emitted + (int64_t)(raw.size() - raw_strung);  // (as the loops emitted them: the loop's edges arrive summed)
+    return SQ_OK;
+}
+}  // namespace
+
+// the host route: the loop on the host threads, then the tail
+static int bwa_raw_edges(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw) {
+    LoopResult L;
+    int rc = bwa_raw_edges_loop(c, hb, c->nodes, false, L);
+    if (rc) return rc;
+    raw.swap(L.raw);
+    return bwa_raw_edges_tail(c, hb, c->nodes, L, raw);
+}
+// the device route (sq_bwa_edges_on_device): the loop as kernels over the resident table, the tail here.  fallback: nothing was done
+static int bwa_raw_edges_device(sq_ctx* c, const HostBatch& hb, std::vector<Edge>& raw, bool& fallback) {
+    BwaEdgesOut D;
+    int rc = dev_bwa_raw_edges(c, c->nodes, D);
+    if (rc == SQ_E_CAPACITY) { fallback = true; return SQ_OK; }
+    if (rc) return rc;
+    fallback = D.fallback;
+    if (fallback) { if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "RawEdges on the device: back to the host loop (%s)\n", D.why); return SQ_OK; }
+    LoopResult L;
+    L.hint = D.final_pos;
+    raw.reserve(D.keys.size());
+    for (size_t i = 0; i < D.keys.size(); ++i) { raw.push_back(edge_unpack(D.keys[i], (int)D.counts[i])); L.n_emitted += (int64_t)D.counts[i]; }
+    L.part.swap(D.part); L.first_dis.swap(D.first_dis); L.second.swap(D.second);
+    for (const unsigned long long key : D.second_keys) L.second_edges.push_back(edge_unpack(key, -1));
+    c->timer.add("bwa_edge_soft_fragments", 0.0, 0.0, D.n_soft);
+    c->timer.add("bwa_edge_lists", 0.0, 0.0, (int64_t)(L.part.size() + L.first_dis.size() + L.second.size()));
+    HostClock hc(c, "host_bwa_raw_edges_tail");
+    return bwa_raw_edges_tail(c, hb, c->nodes, L, raw);
+}
+
+// sq_debug_bwa_raw_edges (see sq_internal.h)
+int bwa_raw_edges_debug(sq_ctx* c, const HostBatch* tables, const std::vector<Node>& N, int route, BwaEdgesDebug& out) {
+    if (!tables && !c->bwa) return fail(c, SQ_E_ARG, "sq_ingest_bwa_file first");
+    const HostBatch& hb = tables ? *tables : *c->bwa;
+    out = BwaEdgesDebug();
+    std::vector<std::pair<unsigned long long, int32_t>> kw;
+    if (route == 0) {
+        LoopResult L;
+        const int rc = bwa_raw_edges_loop(c, hb, N, true, L);
+        if (rc) return rc;
+        for (const Edge& e : L.raw) kw.push_back(std::make_pair((unsigned long long)edge_pack(e), e.w));
+        for (const Edge& e : L.second_edges) out.second_keys.push_back(edge_pack(e));
+        out.part.swap(L.part); out.first_dis.swap(L.first_dis); out.second.swap(L.second);
+        out.final_pos = L.hint; out.n_emitted = L.n_emitted;
+    } else {
+        if (!c->dev) return fail(c, SQ_E_ARG, "no device");
+        if (tables || !c->bwa_resident) {
+            const int rc = dev_bwa_upload(c, hb);
+            if (rc && rc != SQ_E_CAPACITY) return rc;
+            c->bwa_resident = rc == SQ_OK;
+            c->bwa_dev_active = false;
+        }
+        BwaEdgesOut D;
+        const int rc = dev_bwa_raw_edges(c, N, D);
+        if (tables) { dev_clear_records(c); c->bwa_resident = false; }
+        if (rc) return rc;
+        out.fallback = D.fallback; out.n_soft = D.n_soft; out.final_pos = D.final_pos;
+        for (size_t i = 0; i < D.keys.size(); ++i) { kw.push_back(std::make_pair(D.keys[i], (int32_t)D.counts[i])); out.n_emitted += (int64_t)D.counts[i]; }
+        out.part.swap(D.part); out.first_dis.swap(D.first_dis); out.second.swap(D.second); out.second_keys.swap(D.second_keys);
+    }
+    std::sort(kw.begin(), kw.end());
+    for (const auto& x : kw) {
+        if (!out.keys.empty() && out.keys.back() == x.first) out.weights.back() += x.second;
+        else { out.keys.push_back(x.first); out.weights.push_back(x.second); }
+    }
     return SQ_OK;
 }
 
@@ -713,6 +814,15 @@ int bwa_nodes_and_edges(sq_ctx* c, std::vector<Edge>& raw) {
     c->timer.add("bwa_reads_records", 0.0, 0.0, n_reads_records);
     c->snap[1].take(c->nodes, std::vector<Edge>(), nullptr);
     raw.clear();
+    // sq_bwa_edges_on_device: RawEdges' BAM loop over the resident table; a graph it cannot take (no table, equal read offsets inside a
+    // record, an assert of the reference, no memory) keeps the host loop -- same results, same error text
+    if (c->dev && c->bwa_edges_on()) {
+        bool fallback = !c->bwa_resident;
+        if (!fallback) { rc = bwa_raw_edges_device(c, hb, raw, fallback); if (rc) return rc; }
+        c->timer.add("bwa_edges_device_fallback", 0.0, 0.0, fallback ? 1 : 0);
+        if (!fallback) return SQ_OK;
+        raw.clear();
+    }
     { HostClock hc(c, "host_bwa_raw_edges"); rc = bwa_raw_edges(c, hb, raw); }
     return rc;
 }

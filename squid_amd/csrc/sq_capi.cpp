@@ -850,6 +850,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     c->pool.reset(new HostPool(host_workers(p->world_size)));
     if (env_set("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = env_nonzero("SQUID_CHIM_STAGES_GPU") ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
     if (env_set("SQUID_BWA_STAGES_GPU")) c->bwa_dev_env = env_nonzero("SQUID_BWA_STAGES_GPU") ? 1 : 0;    // the same for node depth / breakpoint support of a --bwa context
+    if (env_set("SQUID_BWA_EDGES_GPU")) c->bwa_edges_env = env_nonzero("SQUID_BWA_EDGES_GPU") ? 1 : 0;    // the same for the BAM loop of RawEdges of a --bwa context
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
     *out = c;
@@ -1522,6 +1523,60 @@ int sq_bwa_on_device(sq_ctx* c, int32_t on) {
     if (!c) return SQ_E_ARG;
     c->bwa_dev_asked = on != 0;  // (only a --bwa context looks at it: bwa_dev_on)
     return SQ_OK;
+}
+int sq_bwa_edges_on_device(sq_ctx* c, int32_t on) {
+    if (!c) return SQ_E_ARG;
+    c->bwa_edges_asked = on != 0;  // (only a --bwa context looks at it: bwa_edges_on)
+    return SQ_OK;
+}
+static int bwa_edges_debug_view(sq_ctx* c, const HostBatch* tables, const std::vector<Node>& N, int32_t route, sq_bwa_edges_debug* out) {
+    static thread_local BwaEdgesDebug R;
+    std::memset(out, 0, sizeof *out);
+    const int rc = bwa_raw_edges_debug(c, tables, N, route, R);
+    dev_flush_timers(c);
+    if (rc) return rc;
+    out->n_edges = (int64_t)R.keys.size(); out->keys = (const uint64_t*)R.keys.data(); out->weights = R.weights.data();
+    out->n_part = (int64_t)R.part.size(); out->n_first_dis = (int64_t)R.first_dis.size(); out->n_second = (int64_t)R.second.size();
+    out->part = R.part.data(); out->first_dis = R.first_dis.data(); out->second = R.second.data(); out->second_keys = (const uint64_t*)R.second_keys.data();
+    out->n_emitted = R.n_emitted; out->n_soft = R.n_soft; out->final_pos = R.final_pos; out->fallback = R.fallback ? 1 : 0;
+    return SQ_OK;
+}
+int sq_debug_bwa_raw_edges(sq_ctx* c, int32_t route, sq_bwa_edges_debug* out) {
+    if (!c || !out || (route != 0 && route != 1)) return SQ_E_ARG;
+    return abi_guard(c, "sq_debug_bwa_raw_edges", [&]() -> int {
+        if (!c->bwa || !c->graph_built) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges needs a --bwa context behind sq_build_graph");
+        const GraphSnap& g = c->snap[1];
+        if (g.chr.empty()) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges needs the stage graphs (sq_keep_stage_graphs)");
+        std::vector<Node> N(g.chr.size());
+        for (size_t i = 0; i < N.size(); ++i) N[i] = Node{g.chr[i], g.pos[i], g.len[i], 0, 0.0};
+        return bwa_edges_debug_view(c, nullptr, N, route, out);
+    });
+}
+int sq_debug_bwa_raw_edges_tables(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4,
+                                  sq_bwa_edges_debug* out) {
+    if (!c || !out || (route != 0 && route != 1) || n_nodes < 0 || n_rec < 0 || (n_nodes && !nodes3) || !blk_off || (n_rec && !rec8)) return SQ_E_ARG;
+    return abi_guard(c, "sq_debug_bwa_raw_edges_tables", [&]() -> int {
+        std::vector<Node> N((size_t)n_nodes);
+        for (int32_t i = 0; i < n_nodes; ++i) {
+            N[(size_t)i] = Node{nodes3[3 * i], nodes3[3 * i + 1], nodes3[3 * i + 2], 0, 0.0};
+            if (N[(size_t)i].chr < 0 || (i && N[(size_t)i].chr < N[(size_t)i - 1].chr)) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: node chromosomes must be non-negative and sorted");
+        }
+        if (blk_off[0] != 0) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: blk_off must start at 0");
+        for (int64_t r = 0; r < n_rec; ++r) if (blk_off[r + 1] < blk_off[r]) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: blk_off must not go down");
+        const size_t nb = blk_off[n_rec];
+        if (nb && !blk4) return SQ_E_ARG;
+        if (n_nodes == 0 && n_rec != 0) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: records need a node table");
+        HostBatch hb;
+        for (int64_t r = 0; r < n_rec; ++r) {
+            const int32_t* q = rec8 + 8 * r;
+            hb.refid.push_back(q[0]); hb.pos.push_back(q[1]); hb.mrefid.push_back(q[2]); hb.mpos.push_back(q[3]); hb.endpos.push_back(q[1]);
+            hb.flag.push_back((uint16_t)q[4]); hb.totlen.push_back((uint16_t)q[5]); hb.mapq.push_back((uint8_t)q[6]); hb.aux.push_back((uint8_t)q[7]);
+        }
+        hb.blk_off.assign(blk_off, blk_off + n_rec + 1);
+        hb.name_off.assign((size_t)n_rec + 1, 0);
+        for (size_t b = 0; b < nb; ++b) { hb.b_refpos.push_back(blk4[4 * b]); hb.b_matchref.push_back(blk4[4 * b + 1]); hb.b_readpos.push_back((uint16_t)blk4[4 * b + 2]); hb.b_matchread.push_back((uint16_t)blk4[4 * b + 3]); }
+        return bwa_edges_debug_view(c, &hb, N, route, out);
+    });
 }
 static int sq_debug_bwa_depth_impl(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, int32_t* support, int32_t* sums, int64_t* out2) {
     if (n_nodes < 0 || n_reads < 0 || (n_nodes && (!nodes3 || !support || !sums)) || (n_reads && !reads3) || !out2 || (route != 0 && route != 1) || (route == 1 && !c)) return SQ_E_ARG;

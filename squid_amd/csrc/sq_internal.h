@@ -291,7 +291,12 @@ struct sq_ctx {
     bool bwa_dev_active = false;      // this graph's build had the table and its class bytes: sq_call_sv counts the breakpoint support there
     bool bwa_p3_ready = false;        // the class bytes carry C_P3 for this graph's fragment names
     int64_t bwa_n_p3 = 0;             // records with C_P3
-    bool bwa_dev_on() const { return bwa && (bwa_dev_env >= 0 ? bwa_dev_env != 0 : bwa_dev_asked); }
+    // --bwa: the BAM loop of RawEdges on the device as well (sq_bwa_edges_on_device; SQUID_BWA_EDGES_GPU=1 / =0, read by sq_create, forces / forbids
+    // it); it needs the resident table, so a context with it on behaves as one with sq_bwa_on_device on
+    bool bwa_edges_asked = false;
+    int bwa_edges_env = -1;
+    bool bwa_edges_on() const { return bwa && (bwa_edges_env >= 0 ? bwa_edges_env != 0 : bwa_edges_asked); }
+    bool bwa_dev_on() const { return bwa && (bwa_edges_on() || (bwa_dev_env >= 0 ? bwa_dev_env != 0 : bwa_dev_asked)); }
     // concordant side (device)
     sq::DeviceRecords* dev = nullptr;
     // --bwa (sq_ingest_bwa_file): every record of the one BAM file on the host, with its QNAME (sq_bwa.cpp)
@@ -457,6 +462,19 @@ void bwa_look_bytes(sq_ctx* c, std::vector<uint8_t>& look);          // per reco
 void bwa_name_bytes(sq_ctx* c, std::vector<uint8_t>& in_names);      // per record: the raw QNAME is in the name set of the rebuilt fragments
 void bwa_reads_bytes(const HostBatch& hb, std::vector<uint8_t>& reads);  // per record: it feeds Reads (seed_record_passes)
 void bwa_set_node_depths(std::vector<Node>& N, const std::vector<int32_t>& cnts, const std::vector<int32_t>& sums);
+// sq_debug_bwa_raw_edges(_tables): the BAM loop of RawEdges over the context's batch (or a batch made from the caller's tables: it then takes
+// the place of the resident table, and the context's own batch is uploaded again by the next graph) on the node table `N`, route 0 = the host loop in one go, 1 = the
+// kernels over the resident table (uploaded when it is not there) -- the summed edges sorted by key, the three lists, the would-be edges
+// of the listed second mates, the final position, the number of emitted edges; route 1: the soft fragments and the fallback flag as well
+struct BwaEdgesDebug {
+    std::vector<unsigned long long> keys, second_keys;
+    std::vector<int32_t> weights;
+    std::vector<uint32_t> part, first_dis, second;
+    int32_t final_pos = 0;
+    int64_t n_emitted = 0, n_soft = 0;
+    bool fallback = false;
+};
+int bwa_raw_edges_debug(sq_ctx* c, const HostBatch* tables /* null: the context's batch */, const std::vector<Node>& N, int route, BwaEdgesDebug& out);
 void bwa_node_depth_flat(int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums);  // the depth loop on flat tables
 void reduce_edges(std::vector<Edge>& raw, std::vector<Edge>& out, int threads = 1);
 void filter_by_weight(sq_ctx* c);
@@ -525,6 +543,18 @@ int dev_bwa_upload(sq_ctx* c, const HostBatch& hb);
 int dev_bwa_classify(sq_ctx* c, const uint8_t* in_names, int64_t& n_reads, int64_t& n_p3, int64_t& n_reads_blocks);
 int dev_bwa_node_depth(sq_ctx* c, int n_nodes, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback);
 int dev_bwa_node_depth_flat(sq_ctx* c, int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums, int64_t& held, bool& fallback);
+// --bwa: the BAM loop of RawEdges over the resident table (sq_bwa_edges.inc).  keys / counts: the summed raw edges (edge_pack, any order);
+// part / first_dis / second: record indices in record order (PartialAlign, FirstDisInserted, the multi-aligned second mates whose would-be
+// edge is discordant, with those edges' keys); final_pos: where LocateRead stands behind the last record; fallback: see dev_bwa_raw_edges
+struct BwaEdgesOut {
+    std::vector<unsigned long long> keys, second_keys;
+    std::vector<uint32_t> counts, part, first_dis, second;
+    int32_t final_pos = 0;
+    int64_t n_soft = 0;
+    bool fallback = false;
+    const char* why = "";
+};
+int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& out);
 int dev_chim_download_trimmed(sq_ctx* c);  // the blocks as the device trimmed them, into c->frags
 int dev_connected_components(sq_ctx* c, int n_nodes, const std::vector<Edge>& edges, std::vector<int32_t>& label);
 struct SmallProblem { int n; int eoff, ecount; };  // edges: local u,v,hu,hv,w packed as 5 ints each

@@ -36,6 +36,7 @@
 #include "sq_resolve.inc"
 #include "sq_chim_stage.inc"
 #include "sq_bwa_stage.inc"
+#include "sq_bwa_edges.inc"
 
 #define HIPCHK(call)                                                                                         \
     do {                                                                                                     \
@@ -189,6 +190,12 @@ struct ChimStage {
     DBuf<uint32_t> soft, hist, flags, hval, oval;
     DBuf<unsigned long long> hkey, okey, ekey;
     DBuf<uint8_t> cls;
+    // the --bwa edge stage (sq_bwa_edges.inc, dev_bwa_raw_edges) builds its fragment table on the device and borrows everything else of this
+    // struct (a --bwa context never runs the chimeric device route): off | na | atot | btot, low | rev, the blocks, meta and list bytes, the lists
+    DBuf<uint32_t> e_rec, e_lists;
+    DBuf<int32_t> e_blk;
+    DBuf<uint8_t> e_low, e_rev, e_meta, e_bits;
+    DBuf<unsigned long long> e_skeys;
     uint32_t h_slots = 1u << 12;
     Pinned stage;
     hipEvent_t done = nullptr;
@@ -201,6 +208,7 @@ struct ChimStage {
         table.release(); trim.release(); rn.release(); pin.release(); lastdeep.release(); spos.release(); sout.release(); nodes.release(); hit.release(); goff.release();
         pairs.release(); score.release(); out.release(); soft.release(); hist.release(); flags.release(); hval.release(); oval.release(); hkey.release(); okey.release();
         ekey.release(); cls.release(); stage.release();
+        e_rec.release(); e_lists.release(); e_blk.release(); e_low.release(); e_rev.release(); e_meta.release(); e_bits.release(); e_skeys.release();
         if (done) { (void)hipEventDestroy(done); done = nullptr; }
         version = 0;
     }
@@ -5043,12 +5051,15 @@ static int chim_upload_nodes(sq_ctx* c, const std::vector<Node>& nodes, chs::Nod
     return SQ_OK;
 }
 // classification, the two scans, the soft list and its runs: the position chain of a stage.  flags[4] = number of soft fragments.
-static int chim_chain(sq_ctx* c, const chs::Nodes& N, int stage, chs::Chain& C) {
+// soft_max: the bound of the soft list (the --bwa edge stage sizes it to the table); rows: the three timer rows
+struct ChainRows { const char *classify, *scan, *soft; };
+static constexpr ChainRows CHIM_ROWS{"k_chim_classify", "k_chim_scan", "k_chim_soft"}, BWA_EDGE_ROWS{"k_bwa_edge_classify", "k_bwa_edge_scan", "k_bwa_edge_soft"};
+static int chim_chain(sq_ctx* c, const chs::Nodes& N, int stage, chs::Chain& C, int64_t soft_max, const ChainRows& rows) {
     DeviceRecords& D = *c->dev;
     ChimStage& S = D.chim;
     hipStream_t s = c->stream;
     const int64_t nf = S.nf;
-    const uint32_t cap = (uint32_t)std::min<int64_t>((int64_t)chim_soft_max(), nf);
+    const uint32_t cap = (uint32_t)std::min<int64_t>(soft_max, nf);
     HIPCHK(S.pin.reserve(nf)); HIPCHK(S.lastdeep.reserve(nf)); HIPCHK(S.spos.reserve(nf)); HIPCHK(S.cls.reserve(nf)); HIPCHK(S.soft.reserve(cap + 1)); HIPCHK(S.sout.reserve(cap + 1));
     HIPCHK(S.flags.reserve(8));
     C.pin = S.pin.p; C.lastdeep = S.lastdeep.p; C.spos = S.spos.p; C.soft = S.soft.p; C.sout = S.sout.p; C.cls = S.cls.p; C.soft_cap = cap;
@@ -5056,11 +5067,11 @@ static int chim_chain(sq_ctx* c, const chs::Nodes& N, int stage, chs::Chain& C) 
     const int32_t *refpos = stage == 1 ? F.refpos : S.T.refpos, *readpos = stage == 1 ? F.readpos : S.T.readpos, *matchref = stage == 1 ? F.matchref : S.T.matchref,
                   *matchread = stage == 1 ? F.matchread : S.T.matchread;
     HIPCHK(hipMemsetAsync(S.flags.p, 0, 8 * 4, s));
-    { EvTimer t(c, "k_chim_classify", 13.0 * nf); hipLaunchKernelGGL(k_chim_classify, grid_for(nf, 256), dim3(256), 0, s, N, F, refpos, matchref, stage, C); }
-    { EvTimer t(c, "k_chim_scan", 17.0 * nf);
+    { EvTimer t(c, rows.classify, 13.0 * nf); hipLaunchKernelGGL(k_chim_classify, grid_for(nf, 256), dim3(256), 0, s, N, F, refpos, matchref, stage, C); }
+    { EvTimer t(c, rows.scan, 17.0 * nf);
       HIPCHK((device_scan<OpMax, true>(s, nf, FChimDeep{S.pin.p}, S.lastdeep.p, D.spine, nullptr)));
       HIPCHK((device_scan<OpSum, true>(s, nf, FChimSoft{S.cls.p}, S.spos.p, D.spine, (int32_t*)(S.flags.p + 4)))); }
-    { EvTimer t(c, "k_chim_soft", 5.0 * nf);
+    { EvTimer t(c, rows.soft, 5.0 * nf);
       hipLaunchKernelGGL(k_chim_soft_list, grid_for(nf, 256), dim3(256), 0, s, F, C);
       if (cap) hipLaunchKernelGGL(k_chim_soft_resolve, grid_for(cap, 64), dim3(64), 0, s, N, F, refpos, readpos, matchref, matchread, C, (const uint32_t*)(S.flags.p + 4)); }
     return SQ_OK;
@@ -5082,7 +5093,7 @@ int dev_chimeric_edges(sq_ctx* c, std::vector<Edge>& raw, bool& fallback) {
     chs::Nodes N;
     if ((rc = chim_upload_nodes(c, c->nodes, N))) return rc;
     chs::Chain C;
-    if ((rc = chim_chain(c, N, 1, C))) return rc;
+    if ((rc = chim_chain(c, N, 1, C, (int64_t)chim_soft_max(), CHIM_ROWS))) return rc;
     HIPCHK(S.rn.reserve(std::max<int64_t>(S.nblk, 1)));
     uint32_t* h = S.stage.take_n<uint32_t>(8);
     if (!h) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
@@ -5163,7 +5174,7 @@ int dev_exact_breakpoints_start(sq_ctx* c, bool& fallback) {
     int rc = chim_upload_nodes(c, c->nodes, N);
     if (rc) return rc;
     chs::Chain C;
-    if ((rc = chim_chain(c, N, 2, C))) return rc;
+    if ((rc = chim_chain(c, N, 2, C, (int64_t)chim_soft_max(), CHIM_ROWS))) return rc;
     HIPCHK(hipMemcpyAsync(h, S.flags.p, 8 * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));  // (the soft count decides the route before the blocks are trimmed any further)
     if (h[4] > chim_soft_max()) { fallback = true; return SQ_OK; }
@@ -5343,6 +5354,117 @@ int dev_bwa_node_depth_flat(sq_ctx* c, int32_t n_nodes, const int32_t* nodes3, i
     (void)hipStreamSynchronize(s);
     tab.release(); chr.release(); pack.release();
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ --bwa: RawEdges' record loop on the device
+// (sq_bwa_edges_on_device; the kernels' bodies are in sq_bwa_edges.inc, the position chain is chim_chain over the table made here)
+__global__ __launch_bounds__(256) void k_bwa_frag_count(bwe::Recs R, uint8_t* meta, int32_t* cnt, uint32_t* flags) { bwe::count_record(R, meta, cnt, flags, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_bwa_frag_fill(bwe::Recs R, const uint8_t* meta, bwe::FragsW F) { bwe::fill_record(R, meta, F, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_bwa_edge_fragment(chs::Nodes N, chs::Frags F, chs::Trim T, int32_t* rn, chs::Chain C, chs::Params P, const uint8_t* meta, unsigned long long* hk, uint32_t* hv,
+                                                           uint32_t mask, uint32_t* flags, uint8_t* bits, int32_t* final_pos) {
+    bwe::edge_fragment(N, F, T, rn, C, P, meta, hk, hv, mask, flags, bits, final_pos, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_bwa_edge_lists(chs::Frags F, const int32_t* rn, const uint8_t* bits, const int32_t* at_part, const int32_t* at_first, const int32_t* at_second, uint32_t* l_part,
+                                                        uint32_t* l_first, uint32_t* l_second, unsigned long long* second_keys) {
+    bwe::scatter_lists(F, rn, bits, at_part, at_first, at_second, l_part, l_first, l_second, second_keys, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+struct FBwaBit { const uint8_t* bits; uint8_t bit; __device__ int operator()(int64_t i) const { return (bits[i] & bit) ? 1 : 0; } };
+static_assert(bwe::AUX_MULTI == SQ_AUX_MULTI && bwe::AUX_LOWPHRED == SQ_AUX_LOWPHRED, "sq_bwa_edges.inc restates these");
+static_assert((bwe::FLAG_TIE & (chs::FLAG_FULL | chs::FLAG_ASSERT)) == 0, "one flag word");
+
+// The BAM loop of RawEdges over the resident table of a --bwa batch, on the node table `nodes`.  out.fallback (with out.why): nothing of
+// `out` is valid and the caller takes the host loop -- the table is not resident, two own blocks of a record share a read offset, a
+// block lies behind the last node or an edge would leave the node table (the host loop then fails with the reference's words), or a
+// buffer could not be had.
+int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& out) {
+    out = BwaEdgesOut();
+    auto back = [&](const char* why) { out.fallback = true; out.why = why; return SQ_OK; };
+    if (!c->dev || !c->bwa_resident) return back("the batch is not resident");
+    DeviceRecords& D = *c->dev;
+    ChimStage& S = D.chim;
+    hipStream_t s = c->stream;
+    const int64_t nf = D.n;
+    if (nf == 0) return SQ_OK;
+    if (nodes.empty()) return back("no node");
+    if ((unsigned long long)D.nb + (unsigned long long)nf >= 0x7fffffffull) return back("more than 2^31 block slots");
+    S.version = 0;  // (whatever fragment table the chimeric stages had is gone)
+    S.stage.reset();
+#define BWE_RESERVE(buf, count) do { if ((buf).reserve((size_t)(count)) != hipSuccess) { (void)hipGetLastError(); return back("a device buffer could not be had (SQ_E_CAPACITY)"); } } while (0)
+    BWE_RESERVE(S.e_rec, 4 * (size_t)nf + 8); BWE_RESERVE(S.e_low, nf); BWE_RESERVE(S.e_meta, nf); BWE_RESERVE(S.e_bits, nf);
+    BWE_RESERVE(S.pin, nf); BWE_RESERVE(S.lastdeep, nf); BWE_RESERVE(S.spos, nf); BWE_RESERVE(S.cls, nf); BWE_RESERVE(S.soft, nf + 1); BWE_RESERVE(S.sout, nf + 1); BWE_RESERVE(S.flags, 16);
+    HIPCHK(hipMemsetAsync(S.flags.p, 0, 16 * 4, s));
+    const RecView V = D.view();
+    const bwe::Recs R{nf, V.refid, V.pos, V.mrefid, V.mpos, V.flag, V.totlen, V.mapq, V.aux, V.blk_off, V.b_refpos, V.b_matchref, V.b_readpos, V.b_matchread};
+    bwe::FragsW W{};
+    W.off = S.e_rec.p; W.na = W.off + nf + 1; W.atot = (int32_t*)(W.na + nf); W.btot = W.atot + nf; W.low = S.e_low.p;
+    uint32_t* h = S.stage.take_n<uint32_t>(16);
+    if (!h) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
+    // the fragment table: count -> exclusive scan -> fill (flags[11]: FLAG_TIE of the count kernel, kept apart from the word chim_chain clears)
+    { EvTimer t(c, "k_bwa_frag_count", 14.0 * nf + 2.0 * D.nb); hipLaunchKernelGGL(k_bwa_frag_count, grid_for(nf, 256), dim3(256), 0, s, R, S.e_meta.p, S.pin.p, S.flags.p + 11); }
+    { EvTimer t(c, "k_bwa_frag_scan", 8.0 * nf); HIPCHK((device_scan<OpSum, true>(s, nf, FArr{S.pin.p}, (int32_t*)W.off, D.spine, (int32_t*)(W.off + nf)))); }
+    HIPCHK(hipMemcpyAsync(h, W.off + nf, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + 1, S.flags.p + 11, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h[1] & bwe::FLAG_TIE) return back("two blocks of one record share a read offset");
+    const int64_t nblk = (int64_t)h[0], nb1 = std::max<int64_t>(nblk, 1);
+    if (nblk < 0 || nblk > D.nb + nf) return fail(c, SQ_E_ARG, "internal: the fragment table of the --bwa edge stage is larger than its records allow");
+    BWE_RESERVE(S.e_blk, 5 * nb1); BWE_RESERVE(S.e_rev, nb1); BWE_RESERVE(S.trim, 4 * nb1); BWE_RESERVE(S.rn, nb1);
+    W.refid = S.e_blk.p; W.refpos = W.refid + nb1; W.readpos = W.refpos + nb1; W.matchref = W.readpos + nb1; W.matchread = W.matchref + nb1; W.rev = S.e_rev.p;
+    { EvTimer t(c, "k_bwa_frag_fill", 30.0 * nf + 33.0 * nblk); hipLaunchKernelGGL(k_bwa_frag_fill, grid_for(nf, 256), dim3(256), 0, s, R, S.e_meta.p, W); }
+    S.nf = nf; S.nblk = nblk;
+    chs::Frags& F = S.F;
+    F.nf = nf; F.nblk = nblk; F.off = W.off; F.na = W.na; F.atot = W.atot; F.btot = W.btot; F.low = W.low; F.refid = W.refid; F.rev = W.rev;
+    F.refpos = W.refpos; F.readpos = W.readpos; F.matchref = W.matchref; F.matchread = W.matchread;
+    S.T.refpos = S.trim.p; S.T.readpos = S.trim.p + nb1; S.T.matchref = S.trim.p + 2 * nb1; S.T.matchread = S.trim.p + 3 * nb1;
+    chs::Nodes N;
+    int rc = chim_upload_nodes(c, nodes, N);
+    if (rc) return rc;
+    chs::Chain C;
+    if ((rc = chim_chain(c, N, 1, C, nf, BWA_EDGE_ROWS))) return rc;  // (the soft list holds every fragment: no bound, no fallback)
+    const chs::Params P{c->P.concord_dist_pos, c->P.concord_dist_idx};
+    while (S.h_slots < (1u << 28) && (size_t)S.h_slots < 4 * nodes.size()) S.h_slots <<= 1;
+    for (bool first = true;; first = false) {  // the table starts small and grows when it fills up (unique edges are few)
+        const uint32_t slots = S.h_slots;
+        BWE_RESERVE(S.hkey, slots); BWE_RESERVE(S.hval, slots); BWE_RESERVE(S.okey, slots); BWE_RESERVE(S.oval, slots);
+        HIPCHK(hipMemsetAsync(S.hkey.p, 0xff, (size_t)slots * 8, s));
+        HIPCHK(hipMemsetAsync(S.hval.p, 0, (size_t)slots * 4, s));
+        if (!first) HIPCHK(hipMemsetAsync(S.flags.p, 0, 4 * 4, s));  // (flags[4], the soft count, stays)
+        { EvTimer t(c, "k_bwa_edge_fragment", 12.0 * nf + 45.0 * nblk);
+          hipLaunchKernelGGL(k_bwa_edge_fragment, grid_for(nf, 256), dim3(256), 0, s, N, F, S.T, S.rn.p, C, P, S.e_meta.p, S.hkey.p, S.hval.p, slots - 1, S.flags.p, S.e_bits.p, (int32_t*)(S.flags.p + 6)); }
+        { EvTimer t(c, "k_bwa_edge_compact", 12.0 * slots); hipLaunchKernelGGL(k_hash_compact, grid_for(slots, 256), dim3(256), 0, s, S.hkey.p, S.hval.p, slots, (int32_t*)(S.flags.p + 1), S.okey.p, S.oval.p); }
+        HIPCHK(hipMemcpyAsync(h, S.flags.p, 8 * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (!(h[0] & chs::FLAG_FULL)) break;
+        if (S.h_slots >= (1u << 28)) return back("the edge table is full (SQ_E_CAPACITY)");
+        S.h_slots <<= 2;
+    }
+    if (h[0] & chs::FLAG_ASSERT) return back("a block behind the last node, or an edge that would leave the node table");
+    out.n_soft = (int64_t)h[4];
+    out.final_pos = (int32_t)h[6];
+    const size_t cnt = h[1];
+    // the three lists, in record order: exclusive scans of the list bits (into the chain's arrays, which nothing reads any more), one scatter
+    { EvTimer t(c, "k_bwa_edge_scan", 27.0 * nf);
+      HIPCHK((device_scan<OpSum, true>(s, nf, FBwaBit{S.e_bits.p, bwe::B_PART}, S.pin.p, D.spine, (int32_t*)(S.flags.p + 8))));
+      HIPCHK((device_scan<OpSum, true>(s, nf, FBwaBit{S.e_bits.p, bwe::B_FIRST_DIS}, S.lastdeep.p, D.spine, (int32_t*)(S.flags.p + 9))));
+      HIPCHK((device_scan<OpSum, true>(s, nf, FBwaBit{S.e_bits.p, bwe::B_SECOND}, S.spos.p, D.spine, (int32_t*)(S.flags.p + 10)))); }
+    HIPCHK(hipMemcpyAsync(h + 8, S.flags.p + 8, 3 * 4, hipMemcpyDeviceToHost, s));
+    out.keys.resize(cnt); out.counts.resize(cnt);
+    if (cnt) { HIPCHK(hipMemcpyAsync(out.keys.data(), S.okey.p, cnt * 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(out.counts.data(), S.oval.p, cnt * 4, hipMemcpyDeviceToHost, s)); }
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t n_part = h[8], n_first = h[9], n_second = h[10];
+    if (n_part > (size_t)nf || n_first > (size_t)nf || n_second > (size_t)nf) return fail(c, SQ_E_ARG, "internal: a list of the --bwa edge stage is longer than the table");
+    BWE_RESERVE(S.e_lists, n_part + n_first + n_second + 1); BWE_RESERVE(S.e_skeys, n_second + 1);
+#undef BWE_RESERVE
+    uint32_t *l_part = S.e_lists.p, *l_first = l_part + n_part, *l_second = l_first + n_first;
+    { EvTimer t(c, "k_bwa_edge_lists", 13.0 * nf);
+      hipLaunchKernelGGL(k_bwa_edge_lists, grid_for(nf, 256), dim3(256), 0, s, F, S.rn.p, S.e_bits.p, S.pin.p, S.lastdeep.p, S.spos.p, l_part, l_first, l_second, S.e_skeys.p); }
+    out.part.resize(n_part); out.first_dis.resize(n_first); out.second.resize(n_second); out.second_keys.resize(n_second);
+    { EvTimer t(c, "bwa_edge_download", 12.0 * cnt + 4.0 * (n_part + n_first) + 12.0 * n_second);
+      if (n_part) HIPCHK(hipMemcpyAsync(out.part.data(), l_part, n_part * 4, hipMemcpyDeviceToHost, s));
+      if (n_first) HIPCHK(hipMemcpyAsync(out.first_dis.data(), l_first, n_first * 4, hipMemcpyDeviceToHost, s));
+      if (n_second) { HIPCHK(hipMemcpyAsync(out.second.data(), l_second, n_second * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(out.second_keys.data(), S.e_skeys.p, n_second * 8, hipMemcpyDeviceToHost, s)); } }
+    HIPCHK(hipStreamSynchronize(s));
+    return SQ_OK;
 }
 
 #include "sq_graph_kernels.inc"
