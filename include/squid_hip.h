@@ -194,6 +194,17 @@ int sq_bwa_on_device(sq_ctx* c, int32_t on);
  * and error text (sq_get_timing: bwa_edges_device_fallback counts these; bwa_edge_soft_fragments: the records whose first block had to be
  * resolved in record order; bwa_edge_lists: the entries of the three lists; host_bwa_raw_edges_tail: the host's part). */
 int sq_bwa_edges_on_device(sq_ctx* c, int32_t on);
+/* on != 0: a --bwa context also runs the stream loop of BuildNode_BWA (src/SegmentGraph.cpp:855-1114, the record automaton that emits the seed
+ * nodes) as kernels over the resident record table (squid_amd/csrc/sq_bwa_nodes.inc): the stream is cut at every gap in the coverage, one wave
+ * runs each stretch from a fresh state on the host's guesses and reports what crosses the gap, and the host walks the reports in order and
+ * runs a stretch whose guess was wrong where it counted again with its own automaton.  It implies the resident table, as
+ * sq_bwa_edges_on_device does, and builds no host Reads list (the depth stage reads the table).  Every result is identical to the host
+ * route's.  Default: off.  Accepted on any context; only a --bwa context looks at it.  SQUID_BWA_NODES_GPU=1 / =0 in the environment of
+ * sq_create forces / forbids the route whatever this call says.  A graph whose table is not resident, whose passing records are not sorted by
+ * (RefID, position), whose stretch outgrows a slice, or a device buffer that cannot be had take the host automaton for that graph
+ * (sq_get_timing: bwa_nodes_device_fallback counts these; bwa_node_stretches, bwa_node_stretches_run_again, bwa_node_longest_stretch: the
+ * stretches, those run again on the host, the records of the longest; host_bwa_seed_nodes is absent when the route was taken). */
+int sq_bwa_nodes_on_device(sq_ctx* c, int32_t on);
 
 /* vector<vector<int>> Ordering() -- src/SegmentGraph.cpp:3236-3262: CSR of signed 1-based node ids */
 typedef struct sq_orders {
@@ -373,6 +384,22 @@ typedef struct sq_bwa_edges_debug {
 int sq_debug_bwa_raw_edges(sq_ctx* c, int32_t route, sq_bwa_edges_debug* out);
 int sq_debug_bwa_raw_edges_tables(sq_ctx* c, int32_t route, int32_t n_nodes, const int32_t* nodes3, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4,
                                   sq_bwa_edges_debug* out);
+/* tests: the stream loop of BuildNode_BWA alone, up to the seed nodes.  sq_debug_bwa_seed_nodes: over the batch of a --bwa context (behind
+ * sq_ingest_bwa_file).  sq_debug_bwa_seed_nodes_tables: over caller-supplied record tables (rec8, blk_off, blk4 as for
+ * sq_debug_bwa_raw_edges_tables), which take the place of the context's resident table.  route 0: the host automaton in one go (one stretch,
+ * no guesses); route 1: the kernels of sq_bwa_nodes_on_device with the host's walk over their reports.  The loop starts from the context's
+ * read length (the table form: from read_len) and does not change it.  The result stays valid until the next call on the same thread:
+ * the seeds as {chr, pos, len}, the read length the loop ends with, the records that feed Reads, the flushes of the discordant window that
+ * emitted a node, the marks the zero-coverage rule closed; route 1: the stretches, those run again on the host, those of one record, the
+ * records of the longest, and 1 when the kernels handed the graph back to the host automaton (nothing else is then valid). */
+typedef struct sq_bwa_nodes_debug {
+    int64_t n_seeds;
+    const int32_t* seeds3;
+    int64_t n_reads_records, stretches, again, single, longest, flush_nodes, marks_closed;
+    int32_t read_len, fallback;
+} sq_bwa_nodes_debug;
+int sq_debug_bwa_seed_nodes(sq_ctx* c, int32_t route, sq_bwa_nodes_debug* out);
+int sq_debug_bwa_seed_nodes_tables(sq_ctx* c, int32_t route, int32_t read_len, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4, sq_bwa_nodes_debug* out);
 /* tuning: the two BGZF inflate kernels on the first max_blocks blocks of a file, each ALONE on the device, timed with HIP events (the
  * reader overlaps them with everything else).  variant: 2 = the lane-per-block token pass (k_inflate_tok2), else CH * 100 + PB of the
  * wave-per-block pass (k_inflate_spec: 51211, 51210, 25610, 25611, 38411, 102411).  check != 0 compares every block with zlib.

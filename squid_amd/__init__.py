@@ -27,6 +27,7 @@ EXPORTS = [
     "sq_rccl_available", "sq_rccl_release", "sq_debug_rccl_selftest", "sq_debug_token_bench", "sq_ingest_bwa_file", "sq_junction_sequences", "sq_release_reader_buffers", "sq_keep_host_memory", "sq_keep_stage_graphs",
     "sq_chimeric_on_device", "sq_debug_chim_stages", "sq_bwa_on_device", "sq_debug_bwa_depth",
     "sq_bwa_edges_on_device", "sq_debug_bwa_raw_edges", "sq_debug_bwa_raw_edges_tables",
+    "sq_bwa_nodes_on_device", "sq_debug_bwa_seed_nodes", "sq_debug_bwa_seed_nodes_tables",
 ]
 
 
@@ -82,6 +83,11 @@ class SqBwaEdgesDebug(C.Structure):
                 ("n_emitted", C.c_int64), ("n_soft", C.c_int64), ("final_pos", C.c_int32), ("fallback", C.c_int32)]
 
 
+class SqBwaNodesDebug(C.Structure):
+    _fields_ = [("n_seeds", C.c_int64), ("seeds3", _P32)] + [(k, C.c_int64) for k in ("n_reads_records", "stretches", "again", "single", "longest", "flush_nodes", "marks_closed")] + \
+               [("read_len", C.c_int32), ("fallback", C.c_int32)]
+
+
 class SquidError(RuntimeError):
     pass
 
@@ -122,6 +128,9 @@ def load_library() -> C.CDLL:
         lib.sq_bwa_edges_on_device.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_debug_bwa_raw_edges.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqBwaEdgesDebug)]
         lib.sq_debug_bwa_raw_edges_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _P32, C.c_int64, _P32, C.POINTER(C.c_uint32), _P32, C.POINTER(SqBwaEdgesDebug)]
+        lib.sq_bwa_nodes_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_debug_bwa_seed_nodes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqBwaNodesDebug)]
+        lib.sq_debug_bwa_seed_nodes_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _P32, C.POINTER(C.c_uint32), _P32, C.POINTER(SqBwaNodesDebug)]
         lib.sq_clear_records.argtypes = [C.c_void_p]
         lib.sq_release_reader_buffers.argtypes = [C.c_void_p]
         lib.sq_set_source.argtypes = [C.c_void_p, C.c_char_p]
@@ -272,6 +281,41 @@ class Context:
         """sq_bwa_edges_on_device: a --bwa context also runs the record loop of RawEdges over its batch in HBM (it implies bwa_on_device; same
         results; off by default; any other context ignores it)"""
         self._chk(self.lib.sq_bwa_edges_on_device(self.h, 1 if on else 0), "sq_bwa_edges_on_device")
+
+    def bwa_nodes_on_device(self, on: bool = True):
+        """sq_bwa_nodes_on_device: a --bwa context also runs the record automaton of BuildNode_BWA (the seed nodes) over its batch in HBM (it implies
+        bwa_on_device; same results; off by default; any other context ignores it)"""
+        self._chk(self.lib.sq_bwa_nodes_on_device(self.h, 1 if on else 0), "sq_bwa_nodes_on_device")
+
+    @staticmethod
+    def _bwa_nodes_result(d) -> dict:
+        import numpy as np
+
+        seeds = np.ctypeslib.as_array(d.seeds3, shape=(3 * d.n_seeds,)).reshape(-1, 3).tolist() if d.n_seeds else []
+        return {"seeds": [tuple(x) for x in seeds], "read_len": int(d.read_len), "n_reads_records": int(d.n_reads_records), "stretches": int(d.stretches), "again": int(d.again),
+                "single": int(d.single), "longest": int(d.longest), "flush_nodes": int(d.flush_nodes), "marks_closed": int(d.marks_closed), "fallback": int(d.fallback)}
+
+    def debug_bwa_seed_nodes(self, route: int = 1) -> dict:
+        """sq_debug_bwa_seed_nodes (tests), behind ingest_bwa_file: the record automaton of BuildNode_BWA alone, route 0 = the host automaton in one
+        go, 1 = the kernels over the resident table.  seeds: [(chr, pos, len)]; read_len; n_reads_records; flush_nodes; marks_closed; route 1:
+        stretches, again, single, longest and fallback (1: nothing else is valid)"""
+        d = SqBwaNodesDebug()
+        self._chk(self.lib.sq_debug_bwa_seed_nodes(self.h, route, C.byref(d)), "sq_debug_bwa_seed_nodes")
+        return self._bwa_nodes_result(d)
+
+    def debug_bwa_seed_nodes_tables(self, records, blk_off, blocks, route: int = 1, read_len: int = 0) -> dict:
+        """sq_debug_bwa_seed_nodes_tables (tests): the same on the given record tables (see debug_bwa_raw_edges_tables), which take the place of the
+        context's resident table; read_len: the read length the loop starts with"""
+        import numpy as np
+
+        rc_ = np.ascontiguousarray(np.asarray(records, dtype=np.int32).reshape(-1, 8))
+        bo = np.ascontiguousarray(np.asarray(blk_off, dtype=np.uint32))
+        bl = np.ascontiguousarray(np.asarray(blocks, dtype=np.int32).reshape(-1, 4))
+        assert len(bo) == len(rc_) + 1 and int(bo[-1]) == len(bl)
+        d = SqBwaNodesDebug()
+        self._chk(self.lib.sq_debug_bwa_seed_nodes_tables(self.h, route, read_len, len(rc_), rc_.ctypes.data_as(_P32), bo.ctypes.data_as(C.POINTER(C.c_uint32)), bl.ctypes.data_as(_P32), C.byref(d)),
+                  "sq_debug_bwa_seed_nodes_tables")
+        return self._bwa_nodes_result(d)
 
     @staticmethod
     def _bwa_edges_result(d) -> dict:

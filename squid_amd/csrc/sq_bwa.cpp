@@ -113,7 +113,11 @@ struct SeedRun {
     std::vector<Blk> reads;
     int64_t n_reads_records = 0;  // records that fed `reads`
     std::vector<int> margins;
+    int64_t flush_nodes = 0, marks_closed = 0;  // flushes of the discordant window that emitted a node, marks the zero-coverage rule closed (sq_debug_bwa_seed_nodes)
+    bool keep_reads = true;  // false: the Reads list is not wanted (the device route: the depth stage reads the table)
 };
+// what crosses a gap (bwa_seed_nodes)
+struct Carry { int zero, prev0, mark_start, mark_chr, dis_right, other_right; };
 inline bool seed_record_passes(const HostBatch& hb, size_t ri) {
     const RecRef r{hb, ri};
     return !(r.multi() || hb.mapq[ri] == 0 || r.dup() || !r.mapped() || r.refid() == -1) && r.nblk() != 0;
@@ -137,13 +141,14 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
     if (!opening && ((!dis.none() && r.refid() != dis.head().refid) || (!conc.none() && r.refid() != conc.head().refid) || (!part.none() && r.refid() != part.head().refid))) { other_right = 0; S.oth_set = true; }
     const size_t nb = r.nblk();
     if (nb == 0) return;
-    if (!closing) { for (size_t k = 0; k < nb; ++k) S.reads.push_back(r.blk(k)); ++S.n_reads_records; }
+    if (!closing) { if (S.keep_reads) for (size_t k = 0; k < nb; ++k) S.reads.push_back(r.blk(k)); ++S.n_reads_records; }
     const Blk b0 = r.blk(0), blast = r.blk(nb - 1);
     if (!opening && conc.none() && part.none() && dis.none()) prev0 = r.pos();
     if (!opening && !dis.none() && (dis.v.back().refid != r.refid() || dis_right + RL < r.pos())) {
         // the discordant window is complete: decide the segment boundaries inside it (:888-998)
         int cur_end = 0, cur_start = std::max(prev0, mark_start);
         int d_start = -1, d_end = -1, d_count = -1;
+        const size_t seeds_before = seeds.size();
         bool split = false;
         auto dense = [&]() { return d_start != -1 && !split && d_count > std::min(5.0, 4.0 * (d_end - d_start) / RL); };
         while (!dis.none()) {
@@ -203,6 +208,7 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
         }
         if (dense()) push_node(dis.v[0].refid, d_start, d_end, cur_start, cur_end);  // (W2)
         if (dis.none()) { dis.v.clear(); dis.off = 0; }
+        if (seeds.size() != seeds_before) ++S.flush_nodes;
         conc.drop_left_of(r.refid(), r.pos(), RL); part.drop_left_of(r.refid(), r.pos(), RL);
     }
     // zero coverage in front of this record (:1000-1026)
@@ -216,6 +222,7 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
     }
     if (closing) S.closing_zero = zero;
     if (!opening && zero && mark_start != -1) {
+        ++S.marks_closed;
         if (rightmost > mark_start && rightmost - mark_start < thresh * 20 && !seeds.empty() && mark_start == seeds.back().pos + seeds.back().len) seeds.back().len += rightmost - mark_start;
         else if (rightmost > mark_start && rightmost - mark_start >= thresh * 20) seeds.push_back(Node{mark_chr, mark_start, rightmost - mark_start, 0, 0.0});
         mark_start = -1; mark_chr = -1;
@@ -244,6 +251,23 @@ void seed_step(SeedRun& S, const HostBatch& hb, size_t ri, bool closing, int ope
         w->v.swap(kept); w->off = 0;
         if (w->v.size() == w->cap) w->cap *= 2;
     }
+}
+// one stretch [lo, hi) of the stream: from the state a fresh automaton has and the guesses (first: it opens the stream -- no guess), or from
+// the real state; has_next: record hi closes it
+void run_seed_stretch(SeedRun& S, const HostBatch& hb, size_t lo, size_t hi, bool has_next, bool first, int read_len, int RL_final, int dis_in, const Carry* real, bool keep_reads) {
+    S = SeedRun();
+    S.keep_reads = keep_reads;
+    S.RL = first ? read_len : RL_final;
+    S.counted = first ? 0 : 5;
+    S.dis_right = dis_in;
+    if (real) { S.prev0 = real->prev0; S.mark_start = real->mark_start; S.mark_chr = real->mark_chr; S.dis_right = real->dis_right; S.other_right = real->other_right; }
+    if (keep_reads) {
+        size_t nblk = 0;
+        for (size_t ri = lo; ri < hi; ++ri) nblk += hb.blk_off[ri + 1] - hb.blk_off[ri];
+        S.reads.reserve(nblk);  // (at most every block of the stretch: one allocation)
+    }
+    for (size_t ri = lo; ri < hi; ++ri) seed_step(S, hb, ri, false, (!first && ri == lo) ? (real ? real->zero : 1) : -1);
+    if (has_next) seed_step(S, hb, hi, true);  // (the next stretch's gap record closes this one)
 }
 }  // namespace
 // SQUID_BWA_PIECE=<records>: length of a stretch of the parallel --bwa loops (tests: short stretches and a short warm-up on small inputs); 0: by size
@@ -294,7 +318,6 @@ static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& see
     // the reference compares positions of different chromosomes there (DiscordantRightmost outlives the chromosome, :1002-1013) -- and
     // neither depends on anything the test decides, so every stretch reports what it assigned, the stretches are then walked in order
     // with the real values, and a stretch whose guess was wrong where it counted is run again from the real state.
-    struct Carry { int zero, prev0, mark_start, mark_chr, dis_right, other_right; };
     // DiscordantRightmost is known in advance: it follows a rule of its own -- a discordant record assigns it (or raises it while the
     // discordant window holds something), and the window is emptied by the first record on another chromosome or more than RL behind it --
     // that a pass over (filter, pair type, end of the first block) reproduces, stretch by stretch, each from an empty window (a gap
@@ -317,19 +340,8 @@ static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& see
         for (int k = 0; k < np; ++k) dis_in[(size_t)k + 1] = sum[(size_t)k].first ? sum[(size_t)k].second : dis_in[(size_t)k];
     }
     std::vector<SeedRun> runs((size_t)np);
-    auto work = [&](int k, const Carry* real) {
-        SeedRun& S = runs[(size_t)k];
-        S = SeedRun();
-        S.RL = k == 0 ? c->read_len : RL_final;
-        S.counted = k == 0 ? 0 : 5;
-        S.dis_right = dis_in[(size_t)k];
-        if (real) { S.prev0 = real->prev0; S.mark_start = real->mark_start; S.mark_chr = real->mark_chr; S.dis_right = real->dis_right; S.other_right = real->other_right; }
-        size_t nblk = 0;
-        for (size_t ri = cut[(size_t)k]; ri < cut[(size_t)k + 1]; ++ri) nblk += hb.blk_off[ri + 1] - hb.blk_off[ri];
-        S.reads.reserve(nblk);  // (at most every block of the stretch: one allocation)
-        for (size_t ri = cut[(size_t)k]; ri < cut[(size_t)k + 1]; ++ri) seed_step(S, hb, ri, false, (k > 0 && ri == cut[(size_t)k]) ? (real ? real->zero : 1) : -1);
-        if (k + 1 < np) seed_step(S, hb, cut[(size_t)k + 1], true);  // (the next stretch's gap record closes this one)
-    };
+    const int read_len0 = c->read_len;
+    auto work = [&](int k, const Carry* real) { run_seed_stretch(runs[(size_t)k], hb, cut[(size_t)k], cut[(size_t)k + 1], k + 1 < np, k == 0, read_len0, RL_final, dis_in[(size_t)k], real, true); };
     if (np > 1) c->pool->parallel_for(np, 1 << 20, [&](int k) { work(k, nullptr); }); else work(0, nullptr);
     int again = 0;
     for (int k = 1; k < np; ++k) {
@@ -360,6 +372,122 @@ static int bwa_seed_nodes(sq_ctx* c, const HostBatch& hb, std::vector<Node>& see
     n_reads_records = 0;
     for (SeedRun& S : runs) { seeds.insert(seeds.end(), S.seeds.begin(), S.seeds.end()); reads.push_back(std::move(S.reads)); n_reads_records += S.n_reads_records; }
     c->read_len = runs.back().RL;
+    return SQ_OK;
+}
+
+// ---- the same loop by the kernels of sq_bwa_nodes.inc (sq_bwa_nodes_on_device): the device cuts the stream at every gap record and runs
+// one wave per stretch on the same guesses; here the reports are walked in order with the real values, as above, and a stretch whose
+// guess was wrong where it counted is run again with seed_step from the real state.  No Reads list is built (the depth stage reads the
+// table).  fallback: the kernels raised a flag (or the table is not there) -- nothing was done
+namespace {
+void first_five(const sq_ctx* c, const HostBatch& hb, int32_t rl5[5]) {
+    int rl = c->read_len;
+    for (size_t i = 0; i < 5; ++i) { if (i < hb.size()) rl = std::max(rl, (int)hb.totlen[i]); rl5[i] = rl; }
+}
+}  // namespace
+int bwa_seed_nodes_walk(sq_ctx* c, const HostBatch& hb, const int32_t rl5[5], const BwaNodesOut& D, std::vector<Node>& seeds, int64_t& n_reads_records, int& read_len_out, BwaNodesWalk& W) {
+    const int RL_final = rl5[4];
+    const int np = (int)D.cut.size() - 1;
+    W = BwaNodesWalk();
+    W.stretches = np;
+    n_reads_records = 0;
+    read_len_out = np > 0 ? c->read_len : RL_final;
+    Carry last{1, 0, -1, -1, 0, 0};  // (what the stretch in front left behind: final)
+    SeedRun again;
+    for (int k = 0; k < np; ++k) {
+        const int32_t* R = D.report.data() + (size_t)BNR_ROW * (size_t)k;
+        const size_t lo = (size_t)D.cut[(size_t)k], hi = (size_t)D.cut[(size_t)k + 1];
+        W.single += hi - lo == 1; W.longest = std::max<int64_t>(W.longest, (int64_t)(hi - lo));
+        bool fine = true;
+        int other_right = R[BNR_OTHER_RIGHT];
+        if (k > 0) {
+            fine = last.zero && last.dis_right == D.dis_in[(size_t)k] &&
+                   (last.other_right == 0 || R[BNR_MINPOS_OTH] == INT32_MAX || (long)last.other_right + RL_final < (long)R[BNR_MINPOS_OTH]);
+            if (fine && !(R[BNR_BITS] & 2)) other_right = last.other_right;  // (what the stretch did not assign stays the caller's)
+        }
+        if (fine) {
+            const int32_t* s3 = D.seeds3.data() + 3 * (size_t)R[BNR_SLICE];
+            for (int i = 0; i < R[BNR_SEEDS]; ++i) seeds.push_back(Node{s3[3 * i], s3[3 * i + 1], s3[3 * i + 2], 0, 0.0});
+            n_reads_records += R[BNR_READS];
+            W.flush_nodes += R[BNR_FLUSH_NODES]; W.marks_closed += R[BNR_MARKS_CLOSED];
+            read_len_out = R[BNR_RL];
+            last = Carry{(R[BNR_BITS] & 4) ? 1 : 0, R[BNR_PREV0], R[BNR_MARK_START], R[BNR_MARK_CHR], R[BNR_DIS_RIGHT], other_right};
+            continue;
+        }
+        if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "device stretch %d (%d, %d) again: zero %d, rightmost values %d / %d against %d and first true tests at %d / %d\n", k, hb.refid[lo], hb.pos[lo], last.zero, last.dis_right, last.other_right, D.dis_in[(size_t)k], R[BNR_MINPOS_DIS], R[BNR_MINPOS_OTH]);
+        run_seed_stretch(again, hb, lo, hi, k + 1 < np, k == 0, c->read_len, RL_final, D.dis_in[(size_t)k], &last, false);
+        ++W.again;
+        seeds.insert(seeds.end(), again.seeds.begin(), again.seeds.end());
+        n_reads_records += again.n_reads_records;
+        W.flush_nodes += again.flush_nodes; W.marks_closed += again.marks_closed;
+        read_len_out = again.RL;
+        last = Carry{again.closing_zero ? 1 : 0, again.prev0, again.mark_start, again.mark_chr, again.dis_right, again.other_right};
+    }
+    return SQ_OK;
+}
+namespace {
+int bwa_seed_nodes_device(sq_ctx* c, const HostBatch& hb, std::vector<Node>& seeds, int64_t& n_reads_records, int& read_len_out, bool& fallback, BwaNodesWalk& W) {
+    int32_t rl5[5];
+    first_five(c, hb, rl5);
+    BwaNodesOut D;
+    const int rc = dev_bwa_seed_nodes(c, c->read_len, rl5, D);
+    if (rc == SQ_E_CAPACITY) { fallback = true; return SQ_OK; }
+    if (rc) return rc;
+    fallback = D.fallback;
+    if (fallback) { if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "BuildNode_BWA on the device: back to the host automaton (%s)\n", D.why); return SQ_OK; }
+    HostClock hc(c, "host_bwa_node_walk");
+    return bwa_seed_nodes_walk(c, hb, rl5, D, seeds, n_reads_records, read_len_out, W);
+}
+// the Reads list of :878-881 alone, stretch by stretch (the depth stage fell back behind the device automaton)
+void bwa_reads_list(sq_ctx* c, const HostBatch& hb, std::vector<std::vector<Blk>>& reads) {
+    const size_t nrec = hb.size();
+    const int np = c->pool && nrec > 100000 ? 8 * (c->pool->size() + 1) : 1;
+    reads.assign((size_t)np, std::vector<Blk>());
+    auto part = [&](int k) {
+        std::vector<Blk>& v = reads[(size_t)k];
+        for (size_t ri = nrec * (size_t)k / (size_t)np; ri < nrec * ((size_t)k + 1) / (size_t)np; ++ri) {
+            if (!seed_record_passes(hb, ri)) continue;
+            const RecRef r{hb, ri};
+            for (size_t b = 0; b < r.nblk(); ++b) v.push_back(r.blk(b));
+        }
+    };
+    if (np > 1) c->pool->parallel_for(np, 1 << 20, part); else part(0);
+}
+}  // namespace
+
+// sq_debug_bwa_seed_nodes (see sq_internal.h)
+int bwa_seed_nodes_debug(sq_ctx* c, const HostBatch* tables, int route, BwaNodesDebug& out) {
+    if (!tables && !c->bwa) return fail(c, SQ_E_ARG, "sq_ingest_bwa_file first");
+    const HostBatch& hb = tables ? *tables : *c->bwa;
+    out = BwaNodesDebug();
+    std::vector<Node> seeds;
+    if (route == 0) {
+        int32_t rl5[5];
+        first_five(c, hb, rl5);
+        SeedRun S;
+        run_seed_stretch(S, hb, 0, hb.size(), false, true, c->read_len, rl5[4], 0, nullptr, false);
+        seeds.swap(S.seeds);
+        out.read_len = S.RL; out.n_reads_records = S.n_reads_records; out.stretches = 1; out.longest = (int64_t)hb.size(); out.single = hb.size() == 1;
+        out.flush_nodes = S.flush_nodes; out.marks_closed = S.marks_closed;
+    } else {
+        if (!c->dev) return fail(c, SQ_E_ARG, "no device");
+        if (tables || !c->bwa_resident) {
+            const int rc = dev_bwa_upload(c, hb);
+            if (rc && rc != SQ_E_CAPACITY) return rc;
+            c->bwa_resident = rc == SQ_OK;
+            c->bwa_dev_active = false;
+        }
+        BwaNodesWalk W;
+        int rl = c->read_len;
+        bool fallback = !c->bwa_resident;
+        int rc = SQ_OK;
+        if (!fallback) rc = bwa_seed_nodes_device(c, hb, seeds, out.n_reads_records, rl, fallback, W);
+        if (tables) { dev_clear_records(c); c->bwa_resident = false; }
+        if (rc) return rc;
+        out.fallback = fallback; out.read_len = rl;
+        out.stretches = W.stretches; out.again = W.again; out.single = W.single; out.longest = W.longest; out.flush_nodes = W.flush_nodes; out.marks_closed = W.marks_closed;
+    }
+    for (const Node& n : seeds) { out.seeds3.push_back(n.chr); out.seeds3.push_back(n.pos); out.seeds3.push_back(n.len); }
     return SQ_OK;
 }
 
@@ -783,14 +911,38 @@ int bwa_nodes_and_edges(sq_ctx* c, std::vector<Edge>& raw) {
             up_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         });
     int64_t n_reads_records = 0;
-    { HostClock hc(c, "host_bwa_seed_nodes"); rc = bwa_seed_nodes(c, hb, seeds, reads, n_reads_records); }
-    if (upload.joinable()) {
+    // sq_bwa_nodes_on_device: the automaton over the resident table, so the upload cannot hide behind it (bwa_upload_wait shows all of it); a
+    // graph the kernels hand back (a flag, no table, no memory) takes the host automaton -- same results
+    bool nodes_on_device = false;
+    auto join_upload = [&]() {
+        if (!upload.joinable()) return;
         const auto t0 = std::chrono::steady_clock::now();
         upload.join();
         c->timer.add("bwa_upload", up_ms, 0.0, 1);
         c->timer.add("bwa_upload_wait", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 0.0, 1);  // (what did not hide behind the seed nodes)
         if (up_rc == SQ_OK) c->bwa_resident = true;
+    };
+    rc = SQ_OK;
+    if (c->dev && c->bwa_nodes_on()) {
+        join_upload();
+        bool fallback = !c->bwa_resident;
+        if (!fallback) {
+            BwaNodesWalk W;
+            int rl = c->read_len;
+            rc = bwa_seed_nodes_device(c, hb, seeds, n_reads_records, rl, fallback, W);
+            if (!rc && !fallback) {
+                c->read_len = rl;
+                c->timer.add("bwa_node_stretches", 0.0, 0.0, W.stretches);
+                c->timer.add("bwa_node_stretches_run_again", 0.0, 0.0, W.again);
+                c->timer.add("bwa_node_longest_stretch", 0.0, 0.0, W.longest);
+            }
+        }
+        if (!rc) c->timer.add("bwa_nodes_device_fallback", 0.0, 0.0, fallback ? 1 : 0);
+        nodes_on_device = !rc && !fallback;
+        if (!nodes_on_device) seeds.clear();
     }
+    if (!rc && !nodes_on_device) { HostClock hc(c, "host_bwa_seed_nodes"); rc = bwa_seed_nodes(c, hb, seeds, reads, n_reads_records); }
+    join_upload();
     if (rc) return rc;
     if (up_rc != SQ_OK && up_rc != SQ_E_CAPACITY) return fail(c, up_rc, up_err);  // (only a batch the table cannot hold goes back to the host loops)
     c->counts.read_len = c->read_len;
@@ -810,7 +962,10 @@ int bwa_nodes_and_edges(sq_ctx* c, std::vector<Edge>& raw) {
         }
         c->timer.add("bwa_device_fallback", 0.0, 0.0, fallback ? 1 : 0);
     }
-    if (!on_device) { HostClock hc(c, "host_bwa_node_depth"); bwa_node_depth(c->nodes, reads); }
+    if (!on_device) {
+        if (nodes_on_device) { HostClock hc(c, "host_bwa_reads_list"); bwa_reads_list(c, hb, reads); }  // (the device automaton builds no Reads list)
+        HostClock hc(c, "host_bwa_node_depth"); bwa_node_depth(c->nodes, reads);
+    }
     c->timer.add("bwa_reads_records", 0.0, 0.0, n_reads_records);
     c->snap[1].take(c->nodes, std::vector<Edge>(), nullptr);
     raw.clear();

@@ -851,6 +851,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     if (env_set("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = env_nonzero("SQUID_CHIM_STAGES_GPU") ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
     if (env_set("SQUID_BWA_STAGES_GPU")) c->bwa_dev_env = env_nonzero("SQUID_BWA_STAGES_GPU") ? 1 : 0;    // the same for node depth / breakpoint support of a --bwa context
     if (env_set("SQUID_BWA_EDGES_GPU")) c->bwa_edges_env = env_nonzero("SQUID_BWA_EDGES_GPU") ? 1 : 0;    // the same for the BAM loop of RawEdges of a --bwa context
+    if (env_set("SQUID_BWA_NODES_GPU")) c->bwa_nodes_env = env_nonzero("SQUID_BWA_NODES_GPU") ? 1 : 0;    // the same for the record automaton of BuildNode_BWA of a --bwa context
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
     *out = c;
@@ -1528,6 +1529,58 @@ int sq_bwa_edges_on_device(sq_ctx* c, int32_t on) {
     if (!c) return SQ_E_ARG;
     c->bwa_edges_asked = on != 0;  // (only a --bwa context looks at it: bwa_edges_on)
     return SQ_OK;
+}
+int sq_bwa_nodes_on_device(sq_ctx* c, int32_t on) {
+    if (!c) return SQ_E_ARG;
+    c->bwa_nodes_asked = on != 0;  // (only a --bwa context looks at it: bwa_nodes_on)
+    return SQ_OK;
+}
+// the record tables of the debug entries as a batch of the library's own layout
+static int batch_from_tables(sq_ctx* c, const char* who, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4, HostBatch& hb) {
+    if (blk_off[0] != 0) return fail(c, SQ_E_ARG, std::string(who) + ": blk_off must start at 0");
+    for (int64_t r = 0; r < n_rec; ++r) if (blk_off[r + 1] < blk_off[r]) return fail(c, SQ_E_ARG, std::string(who) + ": blk_off must not go down");
+    const size_t nb = blk_off[n_rec];
+    if (nb && !blk4) return SQ_E_ARG;
+    for (int64_t r = 0; r < n_rec; ++r) {
+        const int32_t* q = rec8 + 8 * r;
+        hb.refid.push_back(q[0]); hb.pos.push_back(q[1]); hb.mrefid.push_back(q[2]); hb.mpos.push_back(q[3]); hb.endpos.push_back(q[1]);
+        hb.flag.push_back((uint16_t)q[4]); hb.totlen.push_back((uint16_t)q[5]); hb.mapq.push_back((uint8_t)q[6]); hb.aux.push_back((uint8_t)q[7]);
+    }
+    hb.blk_off.assign(blk_off, blk_off + n_rec + 1);
+    hb.name_off.assign((size_t)n_rec + 1, 0);
+    for (size_t b = 0; b < nb; ++b) { hb.b_refpos.push_back(blk4[4 * b]); hb.b_matchref.push_back(blk4[4 * b + 1]); hb.b_readpos.push_back((uint16_t)blk4[4 * b + 2]); hb.b_matchread.push_back((uint16_t)blk4[4 * b + 3]); }
+    return SQ_OK;
+}
+static int bwa_nodes_debug_view(sq_ctx* c, const HostBatch* tables, int32_t route, sq_bwa_nodes_debug* out) {
+    static thread_local BwaNodesDebug R;
+    std::memset(out, 0, sizeof *out);
+    const int rc = bwa_seed_nodes_debug(c, tables, route, R);
+    dev_flush_timers(c);
+    if (rc) return rc;
+    out->n_seeds = (int64_t)R.seeds3.size() / 3; out->seeds3 = R.seeds3.data();
+    out->n_reads_records = R.n_reads_records; out->stretches = R.stretches; out->again = R.again; out->single = R.single; out->longest = R.longest;
+    out->flush_nodes = R.flush_nodes; out->marks_closed = R.marks_closed; out->read_len = R.read_len; out->fallback = R.fallback ? 1 : 0;
+    return SQ_OK;
+}
+int sq_debug_bwa_seed_nodes(sq_ctx* c, int32_t route, sq_bwa_nodes_debug* out) {
+    if (!c || !out || (route != 0 && route != 1)) return SQ_E_ARG;
+    return abi_guard(c, "sq_debug_bwa_seed_nodes", [&]() -> int {
+        if (!c->bwa) return fail(c, SQ_E_ARG, "sq_debug_bwa_seed_nodes needs a --bwa context behind sq_ingest_bwa_file");
+        return bwa_nodes_debug_view(c, nullptr, route, out);
+    });
+}
+int sq_debug_bwa_seed_nodes_tables(sq_ctx* c, int32_t route, int32_t read_len, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4, sq_bwa_nodes_debug* out) {
+    if (!c || !out || (route != 0 && route != 1) || read_len < 0 || n_rec < 0 || !blk_off || (n_rec && !rec8)) return SQ_E_ARG;
+    return abi_guard(c, "sq_debug_bwa_seed_nodes_tables", [&]() -> int {
+        HostBatch hb;
+        const int rc = batch_from_tables(c, "sq_debug_bwa_seed_nodes_tables", n_rec, rec8, blk_off, blk4, hb);
+        if (rc) return rc;
+        const int kept = c->read_len;  // (the loop starts from the caller's value; the context keeps its own)
+        c->read_len = read_len;
+        const int rc2 = bwa_nodes_debug_view(c, &hb, route, out);
+        c->read_len = kept;
+        return rc2;
+    });
 }
 static int bwa_edges_debug_view(sq_ctx* c, const HostBatch* tables, const std::vector<Node>& N, int32_t route, sq_bwa_edges_debug* out) {
     static thread_local BwaEdgesDebug R;

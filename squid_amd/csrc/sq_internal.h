@@ -296,7 +296,12 @@ struct sq_ctx {
     bool bwa_edges_asked = false;
     int bwa_edges_env = -1;
     bool bwa_edges_on() const { return bwa && (bwa_edges_env >= 0 ? bwa_edges_env != 0 : bwa_edges_asked); }
-    bool bwa_dev_on() const { return bwa && (bwa_edges_on() || (bwa_dev_env >= 0 ? bwa_dev_env != 0 : bwa_dev_asked)); }
+    // --bwa: the record automaton of BuildNode_BWA on the device as well (sq_bwa_nodes_on_device; SQUID_BWA_NODES_GPU=1 / =0, read by sq_create, forces /
+    // forbids it); it needs the resident table too
+    bool bwa_nodes_asked = false;
+    int bwa_nodes_env = -1;
+    bool bwa_nodes_on() const { return bwa && (bwa_nodes_env >= 0 ? bwa_nodes_env != 0 : bwa_nodes_asked); }
+    bool bwa_dev_on() const { return bwa && (bwa_edges_on() || bwa_nodes_on() || (bwa_dev_env >= 0 ? bwa_dev_env != 0 : bwa_dev_asked)); }
     // concordant side (device)
     sq::DeviceRecords* dev = nullptr;
     // --bwa (sq_ingest_bwa_file): every record of the one BAM file on the host, with its QNAME (sq_bwa.cpp)
@@ -476,6 +481,18 @@ struct BwaEdgesDebug {
 };
 int bwa_raw_edges_debug(sq_ctx* c, const HostBatch* tables /* null: the context's batch */, const std::vector<Node>& N, int route, BwaEdgesDebug& out);
 void bwa_node_depth_flat(int32_t n_nodes, const int32_t* nodes3, int64_t n_reads, const int32_t* reads3, std::vector<int32_t>& cnts, std::vector<int32_t>& sums);  // the depth loop on flat tables
+// sq_debug_bwa_seed_nodes(_tables): the record automaton of BuildNode_BWA alone over the context's batch (or a batch made from the caller's
+// tables, as for bwa_raw_edges_debug), route 0 = the host automaton in one go (one stretch, no guesses), 1 = the kernels of
+// sq_bwa_nodes_on_device with the host's walk over their reports.  The context's read_len is read, not written.
+struct BwaNodesDebug {
+    std::vector<int32_t> seeds3;  // chr, pos, len
+    int32_t read_len = 0;
+    // route 1: stretches, those run again on the host, those of one record, the longest (records); both routes: flushes of the discordant
+    // window that emitted a node, marks the zero-coverage rule closed
+    int64_t n_reads_records = 0, stretches = 0, again = 0, single = 0, longest = 0, flush_nodes = 0, marks_closed = 0;
+    bool fallback = false;
+};
+int bwa_seed_nodes_debug(sq_ctx* c, const HostBatch* tables /* null: the context's batch */, int route, BwaNodesDebug& out);
 void reduce_edges(std::vector<Edge>& raw, std::vector<Edge>& out, int threads = 1);
 void filter_by_weight(sq_ctx* c);
 void filter_by_interleaving(sq_ctx* c, std::vector<uint8_t>& keep);
@@ -555,6 +572,21 @@ struct BwaEdgesOut {
     const char* why = "";
 };
 int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& out);
+// --bwa: the record automaton of BuildNode_BWA over the resident table (sq_bwa_nodes.inc).  read_len: the value the loop starts with, rl5: behind
+// each of the first five records.  cut: np + 1 stretch boundaries; dis_in: the dis_right every stretch was started with; report: np rows of
+// bwn::REPORT values (R_SPARE: where the stretch's seeds start in seeds3, in seeds); fallback: see dev_bwa_seed_nodes
+enum { BNR_RL = 0, BNR_PREV0, BNR_MARK_START, BNR_MARK_CHR, BNR_DIS_RIGHT, BNR_OTHER_RIGHT, BNR_BITS, BNR_MINPOS_DIS, BNR_MINPOS_OTH, BNR_READS, BNR_SEEDS, BNR_FLUSH_NODES, BNR_FLUSHES, BNR_COVER_FAILS,
+       BNR_MARKS_CLOSED, BNR_SLICE, BNR_ROW };  // (bwn::R_*; BNR_BITS: 1 dis_set, 2 oth_set, 4 closing_zero)
+struct BwaNodesOut {
+    std::vector<int32_t> cut, dis_in, report, seeds3;
+    bool fallback = false;
+    const char* why = "";
+};
+int dev_bwa_seed_nodes(sq_ctx* c, int read_len, const int32_t rl5[5], BwaNodesOut& out);
+// the host's walk over the stretch reports in order with the real values (sq_bwa.cpp; also tools/bwa_nodes_emu.cpp, over emulated reports): the
+// seeds strung together, a stretch whose guess was wrong where it counted run again with seed_step
+struct BwaNodesWalk { int64_t stretches = 0, again = 0, single = 0, longest = 0, flush_nodes = 0, marks_closed = 0; };
+int bwa_seed_nodes_walk(sq_ctx* c, const HostBatch& hb, const int32_t rl5[5], const BwaNodesOut& D, std::vector<Node>& seeds, int64_t& n_reads_records, int& read_len_out, BwaNodesWalk& W);
 int dev_chim_download_trimmed(sq_ctx* c);  // the blocks as the device trimmed them, into c->frags
 int dev_connected_components(sq_ctx* c, int n_nodes, const std::vector<Edge>& edges, std::vector<int32_t>& label);
 struct SmallProblem { int n; int eoff, ecount; };  // edges: local u,v,hu,hv,w packed as 5 ints each

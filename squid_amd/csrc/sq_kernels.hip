@@ -37,6 +37,7 @@
 #include "sq_chim_stage.inc"
 #include "sq_bwa_stage.inc"
 #include "sq_bwa_edges.inc"
+#include "sq_bwa_nodes.inc"
 
 #define HIPCHK(call)                                                                                         \
     do {                                                                                                     \
@@ -306,6 +307,12 @@ struct DeviceRecords {
     DBuf<int32_t> bwa_blk_chr, bwa_tmax, bwa_front;
     DBuf<uint8_t> bwa_names;
     DBuf<uint32_t> bwa_acc;
+    // --bwa: BuildNode_BWA's automaton on the device (sq_bwa_nodes.inc): class bytes; first-block start | end | the three ranks; tile maxima
+    // and prefixes; cut list | per-stretch words; the discordant list | flags; the margins and seeds of all stretches
+    DBuf<uint8_t> bwn_cls;
+    DBuf<int32_t> bwn_rec, bwn_str, bwn_margins, bwn_seeds;
+    DBuf<long long> bwn_tiles;
+    DBuf<uint32_t> bwn_dlist;
     // pass 1 (k_pass1): look-back status words, kept records in front of every tile, tile sort keys, the three lists, scalars
     DBuf<int32_t> tile_cnt, tile_K, tile_zcnt2, zc_v, zc_K, zc_refid, zc_pos;
     DBuf<unsigned long long> tile_ob, zc_ob;  // tile_ob: [ntiles] pair of every tile | [ntiles] pair in front of every tile
@@ -3081,6 +3088,7 @@ void dev_destroy(sq_ctx* c) {
     DeviceRecords& D = *c->dev;
     D.chim.release();
     D.bwa_blk_chr.release(); D.bwa_tmax.release(); D.bwa_front.release(); D.bwa_names.release(); D.bwa_acc.release();
+    D.bwn_cls.release(); D.bwn_rec.release(); D.bwn_str.release(); D.bwn_margins.release(); D.bwn_seeds.release(); D.bwn_tiles.release(); D.bwn_dlist.release();
     D.refid.release(); D.pos.release(); D.mrefid.release(); D.mpos.release(); D.endpos.release(); D.b_refpos.release(); D.b_matchref.release();
     D.b_pack.release(); D.n_pack.release(); D.r_pack.release();
     D.flag.release(); D.totlen.release(); D.b_readpos.release(); D.b_matchread.release(); D.mapq.release(); D.aux.release(); D.blk_off.release();
@@ -5463,6 +5471,124 @@ int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& ou
       if (n_part) HIPCHK(hipMemcpyAsync(out.part.data(), l_part, n_part * 4, hipMemcpyDeviceToHost, s));
       if (n_first) HIPCHK(hipMemcpyAsync(out.first_dis.data(), l_first, n_first * 4, hipMemcpyDeviceToHost, s));
       if (n_second) { HIPCHK(hipMemcpyAsync(out.second.data(), l_second, n_second * 4, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(out.second_keys.data(), S.e_skeys.p, n_second * 8, hipMemcpyDeviceToHost, s)); } }
+    HIPCHK(hipStreamSynchronize(s));
+    return SQ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ --bwa: BuildNode_BWA's record automaton on the device
+// (sq_bwa_nodes_on_device; the kernels' bodies are in sq_bwa_nodes.inc)
+__global__ __launch_bounds__(256) void k_bwa_node_class(bwn::Recs R, uint8_t* cls, int32_t* p0, int32_t* e0) { bwn::class_record(R, cls, p0, e0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_bwa_node_tile_max(bwn::Keys K, const uint8_t* cls, int64_t ntiles, long long* tmax) {
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per tile
+    if (tile >= ntiles) return;
+    bwn::tile_max(K, cls, tile, tmax);
+}
+__global__ __launch_bounds__(64) void k_bwa_node_tile_prefix(int64_t ntiles, const long long* tmax, long long* front) { bwn::tile_prefix(ntiles, tmax, front); }
+__global__ __launch_bounds__(256) void k_bwa_node_cut(bwn::Keys K, uint8_t* cls, int64_t ntiles, const long long* front, int rl_final, uint32_t* flags) {
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    bwn::tile_cut(K, cls, tile, front, rl_final, flags);
+}
+__global__ __launch_bounds__(256) void k_bwa_node_scatter(int64_t n, const uint8_t* cls, const int32_t* at_cut, const int32_t* drank, int32_t n_cut, int32_t* cut, uint32_t* dlist) {
+    bwn::scatter(n, cls, at_cut, drank, n_cut, cut, dlist, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_bwa_node_dis(bwn::Tab T, bwn::Par P, const int32_t* cut, int32_t np, int32_t* has, int32_t* dr) { bwn::dis_summary(T, P, cut, np, has, dr, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(64) void k_bwa_node_carry(int32_t np, const int32_t* has, const int32_t* dr, int32_t* dis_in) { bwn::dis_carry(np, has, dr, dis_in); }
+__global__ __launch_bounds__(256) void k_bwa_node_run(bwn::Tab T, bwn::Par P, const int32_t* cut, int32_t np, const int32_t* dis_in, int32_t* margins, int32_t* seeds, int32_t* report, uint32_t* flags) {
+    const int64_t k = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per stretch
+    if (k >= np) return;
+    bwn::run_stretch(T, P, cut, np, dis_in, margins, seeds, report, flags, k);
+}
+__global__ __launch_bounds__(256) void k_bwa_node_gather(int32_t np, int32_t* report, const int32_t* at, const int32_t* seeds, int32_t* out) { bwn::gather_seeds(np, report, at, seeds, out, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+struct FBwnSeeds { const int32_t* report; __device__ int operator()(int64_t k) const { return report[k * bwn::REPORT + bwn::R_SEEDS]; } };
+struct FBwnCls { const uint8_t* cls; uint8_t mask, want; __device__ int operator()(int64_t i) const { return (cls[i] & mask) == want ? 1 : 0; } };
+static_assert(bwn::AUX_MULTI == SQ_AUX_MULTI && bwn::AUX_LOWPHRED == SQ_AUX_LOWPHRED, "sq_bwa_nodes.inc restates these");
+static_assert((int)bwn::REPORT == (int)BNR_ROW && (int)bwn::R_SPARE == (int)BNR_SLICE && (int)bwn::R_BITS == (int)BNR_BITS && (int)bwn::R_SEEDS == (int)BNR_SEEDS && (int)bwn::R_MARKS_CLOSED == (int)BNR_MARKS_CLOSED &&
+              (int)bwn::R_MINPOS_OTH == (int)BNR_MINPOS_OTH && (int)bwn::R_READS == (int)BNR_READS, "the report row of sq_bwa_nodes.inc as sq_bwa.cpp reads it");
+
+// The stream loop of BuildNode_BWA over the resident table of a --bwa batch.  out.fallback (with out.why): nothing of `out` is valid and the
+// caller takes the host automaton -- the table is not resident, the passing records are not sorted by (RefID, pos), a slice of a stretch
+// was too small, or a buffer could not be had.
+int dev_bwa_seed_nodes(sq_ctx* c, int read_len, const int32_t rl5[5], BwaNodesOut& out) {
+    out = BwaNodesOut();
+    auto back = [&](const char* why) { out.fallback = true; out.why = why; return SQ_OK; };
+    if (!c->dev || !c->bwa_resident) return back("the batch is not resident");
+    HIPCHK(hipSetDevice(c->P.device));
+    DeviceRecords& D = *c->dev;
+    hipStream_t s = c->stream;
+    const int64_t n = D.n;
+    if (n == 0) {  // (one empty stretch)
+        out.cut = {0, 0}; out.dis_in = {0}; out.report.assign(BNR_ROW, 0);
+        out.report[BNR_RL] = read_len; out.report[BNR_MARK_START] = -1; out.report[BNR_MARK_CHR] = -1; out.report[BNR_BITS] = 4; out.report[BNR_MINPOS_DIS] = INT32_MAX; out.report[BNR_MINPOS_OTH] = INT32_MAX;
+        return SQ_OK;
+    }
+    if (n >= 0x7ffffff0ll) return back("more than 2^31 records");
+#define BWN_RESERVE(buf, count) do { if ((buf).reserve((size_t)(count)) != hipSuccess) { (void)hipGetLastError(); return back("a device buffer could not be had (SQ_E_CAPACITY)"); } } while (0)
+    const int64_t ntiles = (n + bwn::TILE_RECS - 1) / bwn::TILE_RECS;
+    const size_t n1 = (size_t)n + 1;
+    BWN_RESERVE(D.bwn_cls, n + 4); BWN_RESERVE(D.bwn_rec, 2 * (size_t)n + 3 * n1 + 4); BWN_RESERVE(D.bwn_tiles, 4 * (size_t)ntiles + 4); BWN_RESERVE(D.bwn_dlist, n + 16);
+    int32_t *p0 = D.bwn_rec.p, *e0 = p0 + n, *at_cut = e0 + n, *drank = at_cut + n1, *crank = drank + n1;
+    long long *tmax = D.bwn_tiles.p, *front = tmax + 2 * ntiles;
+    uint32_t *dlist = D.bwn_dlist.p, *flags = dlist + n;  // flags[0]: the kernels' flag word
+    HIPCHK(hipMemsetAsync(flags, 0, 16 * 4, s));
+    const RecView V = D.view();
+    const bwn::Recs R{n, V.refid, V.pos, V.mrefid, V.mpos, V.flag, V.totlen, V.mapq, V.aux, V.blk_off, V.b_refpos, V.b_matchref, V.b_readpos, V.b_matchread};
+    const bwn::Keys K{n, V.refid, V.pos, e0};
+    const dim3 tgrid((unsigned)((ntiles + 3) / 4));
+    { EvTimer t(c, "k_bwa_node_class", 40.0 * n); hipLaunchKernelGGL(k_bwa_node_class, grid_for(n, 256), dim3(256), 0, s, R, D.bwn_cls.p, p0, e0); }
+    { EvTimer t(c, "k_bwa_node_tile_max", 13.0 * n); hipLaunchKernelGGL(k_bwa_node_tile_max, tgrid, dim3(256), 0, s, K, D.bwn_cls.p, ntiles, tmax); }
+    { EvTimer t(c, "k_bwa_node_tile_prefix", 32.0 * ntiles); hipLaunchKernelGGL(k_bwa_node_tile_prefix, dim3(1), dim3(64), 0, s, ntiles, tmax, front); }
+    { EvTimer t(c, "k_bwa_node_cut", 14.0 * n); hipLaunchKernelGGL(k_bwa_node_cut, tgrid, dim3(256), 0, s, K, D.bwn_cls.p, ntiles, front, (int)rl5[4], flags); }
+    { EvTimer t(c, "k_bwa_node_scan", 15.0 * n);
+      HIPCHK((device_scan<OpSum, true>(s, n, FBwnCls{D.bwn_cls.p, bwn::N_CUT, bwn::N_CUT}, at_cut, D.spine, at_cut + n)));
+      HIPCHK((device_scan<OpSum, true>(s, n, FBwnCls{D.bwn_cls.p, bwn::W_MASK, bwn::W_DIS}, drank, D.spine, drank + n)));
+      HIPCHK((device_scan<OpSum, true>(s, n, FBwnCls{D.bwn_cls.p, bwn::W_MASK, bwn::W_PART}, crank, D.spine, crank + n))); }
+    D.pin.reset();
+    uint32_t* h = D.pin.take_n<uint32_t>(8);
+    if (!h) return fail(c, SQ_E_HIP, "hipHostMalloc failed");
+    HIPCHK(hipMemcpyAsync(h, at_cut + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + 1, drank + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + 2, crank + n, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h + 3, flags, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h[3] & bwn::FLAG_UNSORTED) return back("the passing records are not sorted by (RefID, pos)");
+    const int64_t n_cut = h[0], nd = h[1], nc = h[2], np = n_cut + 1;
+    if (n_cut > n || nd > n || nc > n) return fail(c, SQ_E_ARG, "internal: a count of the --bwa node stage is larger than the table");
+    const int64_t seed_slots = 8 * nd + 2 * nc + 4 * np, margin_slots = 2 * nd + nc;
+    if (3 * seed_slots >= 0x7fffffffll) return back("more seed slots than the route holds");
+    // cut (np + 1) | has | dr | dis_in | report (BNR_ROW per stretch)
+    BWN_RESERVE(D.bwn_str, (size_t)np * (4 + BNR_ROW) + 8); BWN_RESERVE(D.bwn_margins, margin_slots + 4); BWN_RESERVE(D.bwn_seeds, 3 * seed_slots + 4);
+#undef BWN_RESERVE
+    int32_t *cut = D.bwn_str.p, *has = cut + np + 1, *dr = has + np, *dis_in = dr + np, *report = dis_in + np;
+    const bwn::Tab T{n, V.refid, V.pos, V.totlen, D.bwn_cls.p, p0, e0, dlist, drank, crank};
+    bwn::Par P;
+    P.read_len = read_len; P.rl_final = rl5[4];
+    for (int i = 0; i < 5; ++i) P.rl5[i] = rl5[i];
+    { EvTimer t(c, "k_bwa_node_scatter", 10.0 * n); hipLaunchKernelGGL(k_bwa_node_scatter, grid_for(n, 256), dim3(256), 0, s, n, D.bwn_cls.p, at_cut, drank, (int32_t)n_cut, cut, dlist); }
+    { EvTimer t(c, "k_bwa_node_dis", 16.0 * np + 16.0 * nd); hipLaunchKernelGGL(k_bwa_node_dis, grid_for(np, 256), dim3(256), 0, s, T, P, cut, (int32_t)np, has, dr); }
+    { EvTimer t(c, "k_bwa_node_carry", 12.0 * np); hipLaunchKernelGGL(k_bwa_node_carry, dim3(1), dim3(64), 0, s, (int32_t)np, has, dr, dis_in); }
+    { EvTimer t(c, "k_bwa_node_run", 17.0 * n + 64.0 * np);
+      hipLaunchKernelGGL(k_bwa_node_run, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, T, P, cut, (int32_t)np, dis_in, D.bwn_margins.p, D.bwn_seeds.p, report, flags); }
+    HIPCHK(hipMemcpyAsync(h + 3, flags, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h[3] & bwn::FLAG_SEEDS_FULL) return back("a stretch emitted more seeds than its slice holds");
+    if (h[3] & bwn::FLAG_MARGINS_FULL) return back("a stretch collected more margins than its slice holds");
+    if (h[3] & bwn::FLAG_GUARD) return back("a flush went round more often than its bound allows");
+    // the seeds in stretch order: exclusive scan of the counts (into `has`, which nothing reads any more), one gather
+    { EvTimer t(c, "k_bwa_node_gather", 8.0 * np); HIPCHK((device_scan<OpSum, true>(s, np, FBwnSeeds{report}, has, D.spine, (int32_t*)(flags + 4)))); }
+    HIPCHK(hipMemcpyAsync(h + 4, flags + 4, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t total = h[4];
+    if (total > seed_slots) return fail(c, SQ_E_ARG, "internal: more seeds than slots in the --bwa node stage");
+    if (D.bwn_margins.reserve(margin_slots + 4 + 3 * (size_t)total) != hipSuccess) { (void)hipGetLastError(); return back("a device buffer could not be had (SQ_E_CAPACITY)"); }
+    int32_t* strung = D.bwn_margins.p;  // (the margins are done with)
+    { EvTimer t(c, "k_bwa_node_gather", 24.0 * total + 12.0 * np); hipLaunchKernelGGL(k_bwa_node_gather, grid_for(np, 256), dim3(256), 0, s, (int32_t)np, report, has, D.bwn_seeds.p, strung); }
+    out.cut.resize((size_t)np + 1); out.dis_in.resize((size_t)np); out.report.resize((size_t)np * BNR_ROW); out.seeds3.resize(3 * (size_t)total);
+    { EvTimer t(c, "bwa_node_download", 4.0 * (np + 1) + 4.0 * np * (1 + BNR_ROW) + 12.0 * total);
+      HIPCHK(hipMemcpyAsync(out.cut.data(), cut, ((size_t)np + 1) * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(out.dis_in.data(), dis_in, (size_t)np * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(out.report.data(), report, (size_t)np * BNR_ROW * 4, hipMemcpyDeviceToHost, s));
+      if (total) HIPCHK(hipMemcpyAsync(out.seeds3.data(), strung, 3 * (size_t)total * 4, hipMemcpyDeviceToHost, s)); }
     HIPCHK(hipStreamSynchronize(s));
     return SQ_OK;
 }
