@@ -356,6 +356,24 @@ int sq_debug_blocks(int32_t n, const int32_t* fields7, uint8_t* rel5, int32_t* p
  * table), pairs in the largest hit group}.  Returns SQ_OK when both routes could be run. */
 int sq_debug_chim_stages(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
                          const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8);
+/* tests: one caller-supplied graph through the small-graph stages of the constructor (src/SegmentGraph.cpp:111-122), by the calls sq_build_graph
+ * makes.  nodes4: n_nodes x {chr, pos, len, support}, sorted; depth3: n_nodes x {AvgDepth, lower bound, upper bound} (the bounds count only with
+ * bounds != 0); edges6: n_edges x {ind1, head1, ind2, head2, weight, groupweight}, sorted by key; keep_in: KeepEdge per edge for a graph that
+ * enters at FilterEdges (null: all kept).  route 0: the host functions, 1: the kernels.  params (may be null): its concord_dist_pos,
+ * concord_dist_idx, min_edge_weight, discordant_ratio and max_allowed_degree take the place of the context's for this call.  Stages first..last of 0 = FilterbyWeight,
+ * 1 = FilterbyInterleaving, 2 = FilterEdges, 3 = CompressNode, 4 = FurtherCompressNode + ConnectedComponent + MultiplyDisEdges.  Afterwards
+ * sq_graph_view hands out the stages that ran (3, 4, 5 as documented there) and, as stage 0, the graph behind the last of them (labels: only
+ * behind stage 4); the context's own graph is gone -- use a context of its own.  out: KeepEdge of FilterbyInterleaving (valid until the next
+ * call on the same thread), 1 when a FilterEdges decision depends on the position inside the depth bounds, 1 when the FurtherCompressNode
+ * kernel handed the graph back to the host function, and SQ_E_ASSERT where the reference would assert (the stages in front of it stay
+ * readable).  Returns SQ_OK when the route could be run. */
+typedef struct sq_graph_stages_debug {
+    int32_t n_keep;
+    const uint8_t* keep;
+    int32_t depth_ambiguous, fallback, rc;
+} sq_graph_stages_debug;
+int sq_debug_graph_stages(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, const double* depth3, int32_t n_edges, const int32_t* edges6, const uint8_t* keep_in, int32_t bounds,
+                          int32_t route, int32_t first, int32_t last, const sq_params* params, sq_graph_stages_debug* out);
 /* tests: the node depth loop of BuildNode_BWA (src/SegmentGraph.cpp:1180-1200) on caller-supplied tables.  nodes3: n_nodes x {chr, pos, len},
  * sorted, the nodes of a chromosome not overlapping; reads3: n_reads x {RefID, RefPos, MatchRef}, the Reads list in its order.  route 0: the host
  * loop (needs no device: c may be null); route 1: the kernels of sq_bwa_on_device.  support / sums: per node the count and the 32-bit sum of

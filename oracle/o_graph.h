@@ -10,6 +10,7 @@
 // Bug-compatibility ledger entries are reproduced and marked "ledger Bn".
 #pragma once
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <limits>
 #include <map>
@@ -92,6 +93,15 @@ inline void CountTop(const Edge_t& e, std::vector<pii>& x) {
 }
 
 struct StageSink;  // optional per-stage dump hook (squid_oracle.cpp)
+
+// A live assert() of the reference that fails on this input.  The normal run says so and exits with `status`; `squid_oracle --graph-stages`
+// (AssertReport() set) prints "ASSERT <line of src/SegmentGraph.cpp>" and exits with 6, so a test can tell the assert from any other end.
+inline bool& AssertReport() { static bool on = false; return on; }
+[[noreturn]] inline void RefAssertFails(int line, int status, const char* what) {
+    if (AssertReport()) { std::printf("ASSERT %d\n", line); std::fflush(stdout); std::exit(6); }
+    std::cerr << what;
+    std::exit(status);
+}
 
 class SegmentGraph_t {
 public:
@@ -1129,7 +1139,7 @@ inline void SegmentGraph_t::FilterEdges(const std::vector<bool>& KeepEdge) {
 inline void SegmentGraph_t::CompressNode() {
     std::vector<int> LinkedNode;
     for (const Edge_t& e : vEdges) { LinkedNode.push_back(e.Ind1); LinkedNode.push_back(e.Ind2); }
-    if (LinkedNode.size() == 0) { std::cout << "Error: 0 nodes are connected by edges.\n"; std::cerr << "oracle: reference asserts here (SegmentGraph.cpp:2537)\n"; std::exit(5); }
+    if (LinkedNode.size() == 0) { if (!AssertReport()) std::cout << "Error: 0 nodes are connected by edges.\n"; RefAssertFails(2537, 5, "oracle: reference asserts here (SegmentGraph.cpp:2537)\n"); }
     std::sort(LinkedNode.begin(), LinkedNode.end());
     LinkedNode.resize(std::distance(LinkedNode.begin(), std::unique(LinkedNode.begin(), LinkedNode.end())));
     std::vector<Node_t> newNodes;
@@ -1256,7 +1266,7 @@ inline void SegmentGraph_t::FurtherCompressNode() {
         }
     }
     for (int i = 0; i + 1 < N; i++)
-        if (!((MergeNode[i] == MergeNode[i + 1]) || (MergeNode[i] + 1 == MergeNode[i + 1]))) { std::cerr << "oracle: MergeNode assertion of SegmentGraph.cpp:2862 fails (reference aborts)\n"; std::exit(4); }
+        if (!((MergeNode[i] == MergeNode[i + 1]) || (MergeNode[i] + 1 == MergeNode[i + 1]))) RefAssertFails(2862, 4, "oracle: MergeNode assertion of SegmentGraph.cpp:2862 fails (reference aborts)\n");
     std::vector<Node_t> newvNodes;
     std::vector<Edge_t> newvEdges;
     int ind = 0;

@@ -236,7 +236,71 @@ static int solve_order_cli(const std::string& method) {
     return 0;
 }
 
+// one graph from stdin through the small-graph stages of the constructor (src/SegmentGraph.cpp:111-122), with the per-stage dumps of the normal
+// run.  Input: "n m", then n lines "chr pos len support avgdepth" (the depth as %.17g or as a hex float) and m lines
+// "ind1 head1 ind2 head2 weight [groupweight [keep]]" sorted by Edge_t::operator<.  Stages, in order: weight (FilterbyWeight), interleave
+// (FilterbyInterleaving), filter (FilterEdges), compress (CompressNode), further (FurtherCompressNode, ConnectedComponent, MultiplyDisEdges);
+// --from / --to pick a stretch of them (a graph that enters behind `weight` brings its group weights, one that enters at `filter` its KeepEdge
+// column).  Exit status 6 with "ASSERT <line>" on stdout where the reference's assert() fails, 2 for input that is no graph.
+static int graph_stages_cli(int argc, char* argv[]) {
+    static const char* const names[5] = {"weight", "interleave", "filter", "compress", "further"};
+    Params P;
+    std::string dumpdir;
+    int from = 0, to = 4;
+    auto stage_of = [&](const char* s) { for (int k = 0; k < 5; k++) if (std::string(s) == names[k]) return k; return -1; };
+    for (int i = 2; i + 1 < argc; i++) {
+        std::string a = argv[i];
+        if (a == "-dp") P.Concord_Dist_Pos = std::atoi(argv[i + 1]);
+        if (a == "-di") P.Concord_Dist_Idx = std::atoi(argv[i + 1]);
+        if (a == "-w") P.Min_Edge_Weight = std::atoi(argv[i + 1]);
+        if (a == "-r") P.DiscordantRatio = std::atof(argv[i + 1]);
+        if (a == "-a") P.MaxAllowedDegree = std::atoi(argv[i + 1]);
+        if (a == "--dump") dumpdir = argv[i + 1];
+        if (a == "--from") from = stage_of(argv[i + 1]);
+        if (a == "--to") to = stage_of(argv[i + 1]);
+    }
+    if (from < 0 || to < from) return 2;
+    std::string line;
+    long n = -1, m = -1;
+    if (!std::getline(std::cin, line) || std::sscanf(line.c_str(), "%ld %ld", &n, &m) != 2 || n < 1 || m < 0) return 2;
+    SegmentGraph_t G(P);
+    G.vNodes.reserve((size_t)n); G.vEdges.reserve((size_t)m);
+    for (long i = 0; i < n; i++) {
+        int c, p, l, s; double d;
+        if (!std::getline(std::cin, line) || std::sscanf(line.c_str(), "%d %d %d %d %lf", &c, &p, &l, &s, &d) != 5) return 2;
+        G.vNodes.push_back(Node_t(c, p, l, s, d));
+    }
+    std::vector<bool> KeepEdge((size_t)m, true);
+    for (long i = 0; i < m; i++) {
+        int a, ha, b, hb, w, gw = 0, keep = 1;
+        if (!std::getline(std::cin, line) || std::sscanf(line.c_str(), "%d %d %d %d %d %d %d", &a, &ha, &b, &hb, &w, &gw, &keep) < 5) return 2;
+        if (a < 0 || b < a || b >= n) return 2;
+        Edge_t e;
+        e.Ind1 = a; e.Head1 = ha != 0; e.Ind2 = b; e.Head2 = hb != 0; e.Weight = w; e.GroupWeight = gw;
+        if (i > 0 && e < G.vEdges.back()) return 2;
+        G.vEdges.push_back(e);
+        KeepEdge[(size_t)i] = keep != 0;
+    }
+    AssertReport() = true;
+    StageSink sink{dumpdir};
+    auto runs = [&](int k) { return from <= k && k <= to; };
+    G.UpdateNodeLink();
+    if (runs(0)) { G.FilterbyWeight(); sink.edges("edges_weight.txt", G.vEdges); }
+    if (runs(1)) { G.FilterbyInterleaving(KeepEdge); sink.edges("edges_interleave.txt", G.vEdges, &KeepEdge); }
+    if (runs(2)) { G.FilterEdges(KeepEdge); sink.edges("edges_filter.txt", G.vEdges); }
+    if (runs(3)) { G.CompressNode(); sink.nodes("nodes_compress.txt", G.vNodes); sink.edges("edges_compress.txt", G.vEdges); }
+    if (runs(4)) {
+        G.FurtherCompressNode();
+        G.ConnectedComponent();
+        G.MultiplyDisEdges();
+        sink.nodes("nodes_final.txt", G.vNodes, &G.Label); sink.edges("edges_final.txt", G.vEdges);
+    }
+    std::printf("%zu\t%zu\n", G.vNodes.size(), G.vEdges.size());
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
+    if (argc >= 2 && std::string(argv[1]) == "--graph-stages") return graph_stages_cli(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "--selftest") return solver_selftest(argc >= 3 ? std::atoi(argv[2]) : 2000);
     if (argc >= 3 && std::string(argv[1]) == "--solve-order") return solve_order_cli(argv[2]);
     if (argc >= 6 && std::string(argv[1]) == "--junction") return oracle::junction::Run(argv[2], argv[3], argv[4], argv[5]);  // utils/JunctionSequence.cpp

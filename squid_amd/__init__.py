@@ -25,7 +25,7 @@ EXPORTS = [
     "sq_set_shard", "sq_exchange_pack", "sq_exchange_unpack", "sq_get_timing", "sq_timing_accumulate", "sq_reset", "sq_ingest_files", "sq_stage_bam", "sq_clear_records", "sq_set_source", "sq_save_records", "sq_load_records", "sq_get_counts", "sq_debug_download", "sq_debug_bp_support", "sq_debug_order", "sq_debug_blocks", "sq_drop_file_cache",
     "sq_total_order", "sq_set_allgather", "sq_rccl_unique_id", "sq_rccl_init", "sq_rccl_attach", "sq_exchange", "sq_exchange_stats",
     "sq_rccl_available", "sq_rccl_release", "sq_debug_rccl_selftest", "sq_debug_token_bench", "sq_ingest_bwa_file", "sq_junction_sequences", "sq_release_reader_buffers", "sq_keep_host_memory", "sq_keep_stage_graphs",
-    "sq_chimeric_on_device", "sq_debug_chim_stages", "sq_bwa_on_device", "sq_debug_bwa_depth",
+    "sq_chimeric_on_device", "sq_debug_chim_stages", "sq_debug_graph_stages", "sq_bwa_on_device", "sq_debug_bwa_depth",
     "sq_bwa_edges_on_device", "sq_debug_bwa_raw_edges", "sq_debug_bwa_raw_edges_tables",
     "sq_bwa_nodes_on_device", "sq_debug_bwa_seed_nodes", "sq_debug_bwa_seed_nodes_tables",
 ]
@@ -88,6 +88,10 @@ class SqBwaNodesDebug(C.Structure):
                [("read_len", C.c_int32), ("fallback", C.c_int32)]
 
 
+class SqGraphStagesDebug(C.Structure):
+    _fields_ = [("n_keep", C.c_int32), ("keep", _PU8), ("depth_ambiguous", C.c_int32), ("fallback", C.c_int32), ("rc", C.c_int32)]
+
+
 class SquidError(RuntimeError):
     pass
 
@@ -123,6 +127,7 @@ def load_library() -> C.CDLL:
         lib.sq_keep_stage_graphs.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_chimeric_on_device.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_debug_chim_stages.argtypes = [C.c_void_p, C.c_int32, _P32, C.c_int32, _P32, C.c_int32, _P32, _P32, _P32, _P32, C.c_int32, _P32, C.POINTER(C.c_int64)]
+        lib.sq_debug_graph_stages.argtypes = [C.c_void_p, C.c_int32, _P32, C.POINTER(C.c_double), C.c_int32, _P32, _PU8, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SqParams), C.POINTER(SqGraphStagesDebug)]
         lib.sq_bwa_on_device.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_debug_bwa_depth.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _P32, C.c_int64, _P32, _P32, _P32, C.POINTER(C.c_int64)]
         lib.sq_bwa_edges_on_device.argtypes = [C.c_void_p, C.c_int32]
@@ -374,6 +379,37 @@ class Context:
                                                 arr(tot), arr(blocks), len(edges), arr([x for e in edges for x in e]), out), "sq_debug_chim_stages")
         keys = ("differences", "host_soft_1", "host_soft_2", "device_soft_1", "device_soft_2", "host_rc", "device_rc", "largest_group")
         return dict(zip(keys, (int(x) for x in out)))
+
+    def debug_graph_stages(self, nodes, edges, route: int = 1, first: int = 0, last: int = 4, bounds: bool = False, keep=None, **params) -> dict:
+        """sq_debug_graph_stages (tests): one graph through the small-graph stages `first`..`last` (0 FilterbyWeight, 1 FilterbyInterleaving,
+        2 FilterEdges, 3 CompressNode, 4 FurtherCompressNode + components + multiplied weights) by the host functions (route 0) or the kernels
+        (route 1).  nodes: [(chr, pos, len, support, depth[, depth_lo, depth_hi])]; edges: [(ind1, head1, ind2, head2, weight[, groupweight])]
+        sorted by key; keep: KeepEdge per edge for a graph that enters at FilterEdges; params: concord_dist_pos, concord_dist_idx, min_edge_weight,
+        discordant_ratio, max_allowed_degree for this call (default: the context's).  graph(3), (4), (5) and (0) then hand out the stages.
+        Uses up the context's graph."""
+        import array
+
+        n, m = len(nodes), len(edges)
+        ni, nd, ei = array.array("i"), array.array("d"), array.array("i")
+        for v in nodes:
+            ni.extend(v[:4])
+            nd.extend((v[4], v[5], v[6]) if len(v) >= 7 else (v[4], v[4], v[4]))
+        for e in edges:
+            ei.extend(e[:5])
+            ei.append(e[5] if len(e) > 5 else 0)
+        ip = lambda a: C.cast(a.buffer_info()[0], _P32) if len(a) else None
+        kb = (C.c_uint8 * max(m, 1))(*[1 if k else 0 for k in keep]) if keep is not None else None
+        out = SqGraphStagesDebug()
+        p = None
+        if params:
+            p = SqParams.from_buffer_copy(self.params)
+            for k, v in params.items():
+                if k not in ("concord_dist_pos", "concord_dist_idx", "min_edge_weight", "discordant_ratio", "max_allowed_degree"):
+                    raise TypeError(f"debug_graph_stages: {k} is not a parameter of the graph stages")
+                setattr(p, k, v)
+        self._chk(self.lib.sq_debug_graph_stages(self.h, n, ip(ni), C.cast(nd.buffer_info()[0], C.POINTER(C.c_double)), m, ip(ei), kb, 1 if bounds else 0, route, first, last,
+                                                 C.byref(p) if p is not None else None, C.byref(out)), "sq_debug_graph_stages")
+        return {"keep": bytes(C.string_at(out.keep, out.n_keep)) if out.n_keep else b"", "depth_ambiguous": int(out.depth_ambiguous), "fallback": int(out.fallback), "rc": int(out.rc)}
 
     def release_reader_buffers(self):
         """give back the device / page-locked memory the GPU reader keeps between ingests (sq_release_reader_buffers)"""

@@ -1381,6 +1381,7 @@ static int sq_build_graph_impl(sq_ctx* c) {
     if (!c->gb) { dev_chim_drop_pending(c); c->chim_s2_pending = false; }
     if (!c->gb && !c->timer_keep) c->timer.clear();
     if (!c->gb) c->ablated = false;
+    c->stage_view = false;
     int rc = c->bwa ? build_graph_bwa(c) : build_graph(c);
     dev_flush_timers(c);
     if (rc <= 0 && c->ablated) {  // (the timers of the run stay readable; its graph does not exist -- whatever the mutilated pass ran into)
@@ -1393,8 +1394,8 @@ static int sq_build_graph_impl(sq_ctx* c) {
 }
 int sq_build_graph(sq_ctx* c) { return abi_guard(c, "sq_build_graph", [&]() { return sq_build_graph_impl(c); }); }
 int sq_graph_view(sq_ctx* c, int32_t stage, sq_graph* g) {
-    if (!c || !g || stage < 0 || stage > 5 || !c->graph_built) return SQ_E_ARG;
-    if (stage != 0 && !c->keep_stages) return fail(c, SQ_E_ARG, "the intermediate graphs were not kept (sq_keep_stage_graphs(ctx, 0) before sq_build_graph)");
+    if (!c || !g || stage < 0 || stage > 5 || (!c->graph_built && !c->stage_view)) return SQ_E_ARG;
+    if (stage != 0 && !c->keep_stages && !c->stage_view) return fail(c, SQ_E_ARG, "the intermediate graphs were not kept (sq_keep_stage_graphs(ctx, 0) before sq_build_graph)");
     c->snap[stage].view(g);
     return SQ_OK;
 }
@@ -1481,7 +1482,7 @@ int sq_reset(sq_ctx* c) {
     c->bwa_dev_active = false;  // (the table stays resident: bwa_resident)
     copy_frags(c, c->frags0, c->frags);  // the graph stages trim the chimeric blocks in place, like the reference does
     c->nodes.clear(); c->edges.clear(); c->label.clear();
-    c->graph_built = false; c->ordered = false;
+    c->graph_built = false; c->ordered = false; c->stage_view = false;
     c->bp_off.clear();
     c->gb.reset(); c->svb.reset(); c->x_pending = false; c->x_ready = false;
     return SQ_OK;
@@ -1654,7 +1655,7 @@ static int sq_debug_chim_stages_impl(sq_ctx* c, int32_t n1, const int32_t* nodes
     if (!c || n1 <= 0 || n2 <= 0 || n_frag < 0 || n_edges < 0 || !nodes1 || !nodes2 || !frag_off || !frag_na || !frag_tot || !blocks6 || (n_edges && !edges4) || !out8) return SQ_E_ARG;
     if (c->bp_future.valid()) (void)c->bp_future.get();
     dev_chim_drop_pending(c);
-    c->chim_s2_pending = false; c->chim_s1_device = false; c->graph_built = false;
+    c->chim_s2_pending = false; c->chim_s1_device = false; c->graph_built = false; c->stage_view = false;
     std::vector<Frag> F0((size_t)n_frag);
     for (int32_t q = 0; q < n_frag; ++q) {
         const int32_t o = frag_off[q], e = frag_off[q + 1], na = frag_na[q];
@@ -1742,6 +1743,85 @@ static int sq_debug_chim_stages_impl(sq_ctx* c, int32_t n1, const int32_t* nodes
 int sq_debug_chim_stages(sq_ctx* c, int32_t n1, const int32_t* nodes1, int32_t n2, const int32_t* nodes2, int32_t n_frag, const int32_t* frag_off, const int32_t* frag_na,
                          const int32_t* frag_tot, const int32_t* blocks6, int32_t n_edges, const int32_t* edges4, int64_t* out8) {
     return abi_guard(c, "sq_debug_chim_stages", [&]() { return sq_debug_chim_stages_impl(c, n1, nodes1, n2, nodes2, n_frag, frag_off, frag_na, frag_tot, blocks6, n_edges, edges4, out8); });
+}
+// (tests) one caller-supplied graph through the small-graph stages, by the calls build_graph / finish_graph make
+static int sq_debug_graph_stages_impl(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, const double* depth3, int32_t n_edges, const int32_t* edges6, const uint8_t* keep_in,
+                                      int32_t bounds, int32_t route, int32_t first, int32_t last, const sq_params* params, sq_graph_stages_debug* out) {
+    if (!c || !out || n_nodes <= 0 || n_edges < 0 || !nodes4 || !depth3 || (n_edges && !edges6) || route < 0 || route > 1 || first < 0 || last > 4 || first > last) return SQ_E_ARG;
+    if (c->bp_future.valid()) (void)c->bp_future.get();
+    dev_chim_drop_pending(c);
+    c->chim_s2_pending = false; c->chim_s1_device = false; c->graph_built = false; c->ordered = false; c->stage_view = false;
+    c->gb.reset();
+    std::vector<Node> N((size_t)n_nodes);
+    for (int32_t i = 0; i < n_nodes; ++i) {
+        const int32_t* v = nodes4 + 4 * (size_t)i;
+        const double* d = depth3 + 3 * (size_t)i;
+        if (v[2] <= 0 || (i > 0 && (v[0] < nodes4[4 * (size_t)(i - 1)]))) return fail(c, SQ_E_ARG, "sq_debug_graph_stages: node table is not sorted, or holds an empty node");
+        N[(size_t)i] = Node{v[0], v[1], v[2], v[3], d[0], d[1], d[2]};
+    }
+    std::vector<Edge> E((size_t)n_edges);
+    for (int32_t i = 0; i < n_edges; ++i) {
+        const int32_t* e = edges6 + 6 * (size_t)i;
+        if (e[0] < 0 || e[2] < e[0] || e[2] >= n_nodes) return fail(c, SQ_E_ARG, "sq_debug_graph_stages: edge outside the node table");
+        Edge& x = E[(size_t)i];
+        x.a = e[0]; x.ha = e[1] != 0; x.b = e[2]; x.hb = e[3] != 0; x.w = e[4]; x.gw = e[5];
+        if (i > 0 && edge_key_less(x, E[(size_t)i - 1])) return fail(c, SQ_E_ARG, "sq_debug_graph_stages: edges are not sorted by key");
+    }
+    c->nodes.swap(N); c->edges.swap(E); c->label.clear();
+    const sq_params saved = c->P;
+    if (params) {  // the five parameters the stages read, for this call only
+        c->P.concord_dist_pos = params->concord_dist_pos; c->P.concord_dist_idx = params->concord_dist_idx; c->P.min_edge_weight = params->min_edge_weight;
+        c->P.discordant_ratio = params->discordant_ratio; c->P.max_allowed_degree = params->max_allowed_degree;
+    }
+    c->depth_bounds = bounds != 0; c->depth_ambiguous = false;
+    const bool host = route == 0;
+    static thread_local std::vector<uint8_t> keep;
+    keep.assign((size_t)n_edges, 1);
+    if (keep_in) keep.assign(keep_in, keep_in + n_edges);
+    *out = sq_graph_stages_debug{0, nullptr, 0, 0, 0};
+    auto runs = [&](int k) { return first <= k && k <= last; };
+    int rc = SQ_OK;
+    bool labelled = false;
+    do {
+        if (runs(0)) {
+            if (host) filter_by_weight(c); else if ((rc = dev_filter_by_weight(c))) break;
+            c->snap[3].take(c->nodes, c->edges, nullptr);
+        }
+        if (runs(1)) { if (host) filter_by_interleaving(c, keep); else if ((rc = dev_filter_by_interleaving(c, keep))) break; }
+        if (runs(2)) {
+            if (keep.size() != c->edges.size()) { rc = fail(c, SQ_E_ARG, "sq_debug_graph_stages: no KeepEdge column for the edges in front of FilterEdges"); break; }
+            if (host) filter_edges(c, keep); else if ((rc = dev_filter_edges(c, keep))) break;
+            c->snap[4].take(c->nodes, c->edges, nullptr);
+        }
+        if (runs(3)) {
+            if ((rc = host ? compress_nodes(c) : dev_compress_nodes(c))) break;
+            c->snap[5].take(c->nodes, c->edges, nullptr);
+        }
+        if (runs(4)) {  // (as finish_graph)
+            rc = host ? further_compress(c) : dev_further_compress(c);
+            if (rc == 2) { out->fallback = 1; rc = further_compress(c); }
+            if (rc) break;
+            if ((rc = dev_connected_components(c, (int)c->nodes.size(), c->edges, c->label))) break;
+            multiply_discordant(c, false);
+            labelled = true;
+        }
+    } while (false);
+    dev_flush_timers(c);
+    c->P = saved;
+    out->n_keep = (int32_t)keep.size(); out->keep = keep.data();
+    out->depth_ambiguous = c->depth_ambiguous ? 1 : 0;
+    c->depth_bounds = false; c->depth_ambiguous = false;
+    if (rc && rc != SQ_E_ASSERT) return rc;
+    out->rc = rc;
+    c->err.clear();
+    c->snap[0].take(c->nodes, c->edges, labelled ? &c->label : nullptr);
+    c->nodes.clear(); c->edges.clear(); c->label.clear();
+    c->stage_view = true;
+    return SQ_OK;
+}
+int sq_debug_graph_stages(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, const double* depth3, int32_t n_edges, const int32_t* edges6, const uint8_t* keep_in, int32_t bounds,
+                          int32_t route, int32_t first, int32_t last, const sq_params* params, sq_graph_stages_debug* out) {
+    return abi_guard(c, "sq_debug_graph_stages", [&]() { return sq_debug_graph_stages_impl(c, n_nodes, nodes4, depth3, n_edges, edges6, keep_in, bounds, route, first, last, params, out); });
 }
 int sq_debug_order(sq_ctx* c, int32_t n, int32_t n_edges, const int32_t* edges5, int32_t use_gpu, int32_t* mask, int32_t* order, int64_t* value) {
     if (!c || n_edges < 0 || (n_edges && !edges5) || !mask || !order || !value) return SQ_E_ARG;

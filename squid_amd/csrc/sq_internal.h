@@ -313,6 +313,7 @@ struct sq_ctx {
     std::vector<int32_t> label;
     sq::GraphSnap snap[6];
     bool graph_built = false, ordered = false;
+    bool stage_view = false;  // the snapshots hold the stages of sq_debug_graph_stages: sq_graph_view hands them out, nothing else may use them
     // SQUID_REPLAY_CHECK: every break candidate the segmentation replay tests (SegmentGraph.cpp:440-481) is counted a second time with the
     // reference's linear passes over the same windows and compared with the binary-search / span-index counts the replay uses
     mutable std::atomic<long long> replay_checked{0}, replay_mismatch{0};

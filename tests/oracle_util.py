@@ -33,6 +33,36 @@ def read_edges(path):
     return rows
 
 
+GRAPH_STAGES = ("weight", "interleave", "filter", "compress", "further")
+
+
+def graph_stages(build_dir, text, dump, flags, first=0, last=4):
+    """one graph (the text of tests/graphs.py oracle_text) through `squid_oracle --graph-stages`, stages first..last (indices into
+    GRAPH_STAGES).  Returns a dict with the stages that ran, read from the dumps: weight / filter: edge rows, keep: [bool], compress:
+    (nodes, edges), final: (nodes with label, edges), assert: the line of the reference's assert when it ended there (status 6)"""
+    dump = Path(dump)
+    dump.mkdir(parents=True, exist_ok=True)
+    cmd = [str(Path(build_dir) / "squid_oracle"), "--graph-stages", *flags, "--dump", str(dump), "--from", GRAPH_STAGES[first], "--to", GRAPH_STAGES[last]]
+    r = subprocess.run(cmd, input=text, capture_output=True, text=True)
+    out = {}
+    if r.returncode == 6:
+        out["assert"] = int(r.stdout.split("ASSERT")[1].split()[0])
+    elif r.returncode:
+        raise subprocess.CalledProcessError(r.returncode, cmd, r.stdout, r.stderr)
+    ran = lambda k, f: first <= k <= last and (dump / f).exists()
+    if ran(0, "edges_weight.txt"):
+        out["weight"] = read_edges(dump / "edges_weight.txt")
+    if ran(1, "edges_interleave.txt"):
+        out["keep"] = [bool(r[6]) for r in read_edges(dump / "edges_interleave.txt")]
+    if ran(2, "edges_filter.txt"):
+        out["filter"] = read_edges(dump / "edges_filter.txt")
+    if ran(3, "nodes_compress.txt"):
+        out["compress"] = (read_nodes(dump / "nodes_compress.txt"), read_edges(dump / "edges_compress.txt"))
+    if ran(4, "nodes_final.txt"):
+        out["final"] = (read_nodes(dump / "nodes_final.txt"), read_edges(dump / "edges_final.txt"))
+    return out
+
+
 def read_orders(path):
     out = []
     for line in Path(path).read_text().splitlines():

@@ -931,7 +931,8 @@ def test_oracle_exact_breakpoints_against_the_literal_loop(built, synth, tmp_pat
 
 # ---- SegmentGraph.cpp:2394-2527: GroupConnection, GroupSelect, FilterEdges (and UpdateNodeLink :2894-2910 for the per-node edge lists);
 # Min_Edge_Weight 5, MaxAllowedDegree 5, Concord_Dist_Pos 50000, Concord_Dist_Idx 20 (Config.cpp:24-28)
-def _filter_edges_literal(nodes, edges, keep, min_w=5, max_deg=5, dist_pos=50000, dist_idx=20):
+def _filter_edges_literal(nodes, edges, keep, min_w=5, max_deg=5, dist_pos=50000, dist_idx=20, trace=None):
+    """trace: a dict that receives what the result alone does not show (tests/test_graph_stage_fuzz.py counts its seed list's coverage with it)"""
     chr_, pos, ln, depth = [n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes], [n[4] for n in nodes]
     head, tail = [[] for _ in nodes], [[] for _ in nodes]
     for e in edges:  # e = (Ind1, Head1, Ind2, Head2, Weight, GroupWeight)
@@ -987,6 +988,8 @@ def _filter_edges_literal(nodes, edges, keep, min_w=5, max_deg=5, dist_pos=50000
                 lb = label[conn.index(e[0] if e[0] != node else e[2])]
                 if lb != maxlabel and lb != 0:
                     todelete.append(e)
+                    if trace is not None:
+                        trace["group_select_deletions"] = trace.get("group_select_deletions", 0) + 1
 
     bad, todelete = [], []
     for i in range(len(nodes)):
@@ -1006,6 +1009,8 @@ def _filter_edges_literal(nodes, edges, keep, min_w=5, max_deg=5, dist_pos=50000
     okey = lambda e: (e[0], e[2], e[1], e[3])  # Edge_t::operator<
     todelete.sort(key=okey)
     bad = set(bad)
+    if trace is not None:
+        trace["bad_nodes"] = bad
     tmp = []
     for i, e in enumerate(edges):
         cond1, cond2 = False, True
@@ -1019,6 +1024,10 @@ def _filter_edges_literal(nodes, edges, keep, min_w=5, max_deg=5, dist_pos=50000
             ratio = num / den if den != 0 else (float("inf") if num > 0 else float("nan"))  # (what the double division gives)
             if (e[4] <= min_w + 2 and ratio > 3) or (e[4] > min_w + 2 and ratio > 50):
                 cond2 = False
+                if trace is not None and keep[i]:
+                    trace["ratio_deletions"] = trace.get("ratio_deletions", 0) + 1
+            elif trace is not None and keep[i] and ratio != ratio:
+                trace["nan_ratio_kept"] = trace.get("nan_ratio_kept", 0) + 1
         if keep[i] and cond1 and cond2:
             tmp.append(e)
     tmp.sort(key=okey)
@@ -1054,7 +1063,7 @@ def test_oracle_filter_edges_against_the_literal_loop(built, synth, tmp_path, cf
 
 # ---- SegmentGraph.cpp:1968-2124, statement by statement, its slips included (`vEdges[i].Ind1` / `vEdges[i].Ind2` where the neighbour j is
 # meant at :2002, :2006, :2021, :2054, and the forward loop's opposite-orientation branch moving the lower ends of its ranges, :2058-2059)
-def _filter_by_weight_literal(nodes, edges, min_w=5, dist_pos=50000, dist_idx=20):
+def _filter_by_weight_literal(nodes, edges, min_w=5, dist_pos=50000, dist_idx=20, trace=None):
     chr_, pos, ln = [n[0] for n in nodes], [n[1] for n in nodes], [n[2] for n in nodes]
     E = [list(e[:6]) for e in edges]  # [Ind1, Head1, Ind2, Head2, Weight, GroupWeight]
     n = len(E)
@@ -1099,6 +1108,8 @@ def _filter_by_weight_literal(nodes, edges, min_w=5, dist_pos=50000, dist_idx=20
                 elif ej[1] != ei[1] and ej[3] != ei[3]:
                     if is_disc(ej) and ej[2] >= I2o[0] - dist_idx and ei[2] <= I2o[1] + dist_idx and np2 >= P2o[0] - dist_pos and np2 <= P2o[1] + dist_pos:
                         near.append(j)
+                        if trace is not None:
+                            trace["opposite_joins"] = trace.get("opposite_joins", 0) + 1
                         I1o[0] = min(I1o[0], ej[0]); P1o[0] = min(P1o[0], np1)
                         I2o[0] = min(I2o[0], ej[2]); I2o[1] = max(I2o[1], ej[2])
                         P2o[0] = min(P2o[0], np2); P2o[1] = max(P2o[1], np2)
@@ -1122,6 +1133,8 @@ def _filter_by_weight_literal(nodes, edges, min_w=5, dist_pos=50000, dist_idx=20
                 elif ej[1] != ei[1] and ej[3] != ei[3]:
                     if is_disc(ej) and ej[2] >= I2o[0] - dist_idx and ei[2] <= I2o[1] + dist_idx and np2 >= P2o[0] - dist_pos and np2 <= P2o[1] + dist_pos:
                         near.append(j)
+                        if trace is not None:
+                            trace["opposite_joins"] = trace.get("opposite_joins", 0) + 1
                         I1o[0] = min(I1o[0], ej[0]); P1o[0] = min(P1o[0], np1)
                         I2o[0] = min(I2o[0], ej[2]); I2o[1] = max(I2o[1], ej[2])
                         P2o[0] = min(P2o[0], np2); P2o[1] = max(P2o[1], np2)
@@ -1135,6 +1148,8 @@ def _filter_by_weight_literal(nodes, edges, min_w=5, dist_pos=50000, dist_idx=20
                     E[k][5] = s if E[k][5] < s else E[k][5]
                     seen[k] = True
             else:
+                if trace is not None:
+                    trace["long_groups"] = trace.get("long_groups", 0) + 1
                 for k in near:
                     E[k][5] = E[k][4]
                     seen[k] = True
