@@ -206,6 +206,19 @@ int sq_bwa_edges_on_device(sq_ctx* c, int32_t on);
  * stretches, those run again on the host, the records of the longest; host_bwa_seed_nodes is absent when the route was taken). */
 int sq_bwa_nodes_on_device(sq_ctx* c, int32_t on);
 
+/* on != 0: the control automaton of BuildNode_STAR (src/SegmentGraph.cpp:354-646, which turns every passed discordant cluster into seed nodes) runs
+ * as a kernel (squid_amd/csrc/sq_segment_stage.inc) in place of the host replay: one wave runs each active stretch of the concordant stream from a
+ * fresh state on the guess that a node exists in front and is too far away to matter, and reports what the guess rested on; the host walks the
+ * reports in stretch order with the real last node and runs a stretch whose report does not hold, or that outgrew a capacity (margin list,
+ * nodes, sens list), again with its own automaton behind exactly that node.  Every result is identical to the host route's.  Default: off.
+ * Accepted on any context; only a STAR context looks at it, a --bwa context ignores it.  A chromosome-sharded context (sq_set_shard) keeps the
+ * host replay whatever the switch says: the sharded hypotheses A/B/C stay host work.  SQUID_SEGMENT_GPU=1 / =0 in the environment of sq_create
+ * forces / forbids the route whatever this call says.  SQUID_REPLAY_CHECK stays a facility of the host route: with the device route on its two
+ * counters stay 0.  A plan too large for the route's tables takes the whole pass back to the host replay (sq_get_timing:
+ * segment_device_fallback counts these; segment_stretches, segment_stretches_run_again, segment_longest_stretch: the active stretches, those
+ * run again on the host, the records of the longest; k_seg_run, host_segment_walk; host_segment_replay is absent when the route was taken). */
+int sq_segment_on_device(sq_ctx* c, int32_t on);
+
 /* vector<vector<int>> Ordering() -- src/SegmentGraph.cpp:3236-3262: CSR of signed 1-based node ids */
 typedef struct sq_orders {
     int32_t n_components;
@@ -418,6 +431,26 @@ typedef struct sq_bwa_nodes_debug {
 } sq_bwa_nodes_debug;
 int sq_debug_bwa_seed_nodes(sq_ctx* c, int32_t route, sq_bwa_nodes_debug* out);
 int sq_debug_bwa_seed_nodes_tables(sq_ctx* c, int32_t route, int32_t read_len, int64_t n_rec, const int32_t* rec8, const uint32_t* blk_off, const int32_t* blk4, sq_bwa_nodes_debug* out);
+/* tests: the segmentation automaton of BuildNode_STAR alone, up to the seed nodes.  sq_debug_segment_seeds: the context's own records and fragments
+ * through prepare plus replay (a STAR context, not sharded).  sq_debug_segment_seeds_tables: the automaton's inputs as plain arrays -- recs6: the
+ * kept stream, one (RefID, position, first block's refpos, matchref, readpos, class bits: 2 concordant, 4 partially aligned, 8 reverse, 16 mate)
+ * per record; disc4: the sorted discordant blocks (refid, refpos, matchref, reverse); part2: the sorted clip positions (refid, position); the
+ * cluster table is built from the blocks and must have n_clusters entries; rest_off / rest_pos / rest_len: the ConcordRest candidates per cluster
+ * sorted by refpos; trigger: per cluster, the kept index of the first record beyond it (n_recs: none); zero3: the zero-coverage records (kept
+ * index, otherChr, otherright in front of it).  route 0: the host automaton in one go, serial; route 1: the kernel of sq_segment_on_device with
+ * the host's walk over its reports.  The result stays valid until the next call on the same thread: the seeds as {chr, pos, len} in order, the
+ * active stretches, those run again on the host, the records of the longest, the sens values the kept stretches reported, the nodes extended
+ * (out.back().len += ...), the stretches kept that emitted a node, those that hit a capacity, and 1 when the plan went back to the host. */
+typedef struct sq_segment_debug {
+    int64_t n_seeds;
+    const int32_t* seeds3;
+    int64_t stretches, again, longest, sens, extended, kept_with_nodes, flagged;
+    int32_t fallback;
+} sq_segment_debug;
+int sq_debug_segment_seeds(sq_ctx* c, int32_t route, sq_segment_debug* out);
+int sq_debug_segment_seeds_tables(sq_ctx* c, int32_t route, int32_t read_len, int64_t n_recs, const int32_t* recs6, int32_t n_disc, const int32_t* disc4, int32_t n_part, const int32_t* part2,
+                                  int32_t n_clusters, const int32_t* rest_off, const int32_t* rest_pos, const int32_t* rest_len, const int32_t* trigger, int32_t n_zero, const int32_t* zero3,
+                                  sq_segment_debug* out);
 /* tuning: the two BGZF inflate kernels on the first max_blocks blocks of a file, each ALONE on the device, timed with HIP events (the
  * reader overlaps them with everything else).  variant: 2 = the lane-per-block token pass (k_inflate_tok2), else CH * 100 + PB of the
  * wave-per-block pass (k_inflate_spec: 51211, 51210, 25610, 25611, 38411, 102411).  check != 0 compares every block with zlib.

@@ -28,6 +28,7 @@ EXPORTS = [
     "sq_chimeric_on_device", "sq_debug_chim_stages", "sq_debug_graph_stages", "sq_bwa_on_device", "sq_debug_bwa_depth",
     "sq_bwa_edges_on_device", "sq_debug_bwa_raw_edges", "sq_debug_bwa_raw_edges_tables",
     "sq_bwa_nodes_on_device", "sq_debug_bwa_seed_nodes", "sq_debug_bwa_seed_nodes_tables",
+    "sq_segment_on_device", "sq_debug_segment_seeds", "sq_debug_segment_seeds_tables",
 ]
 
 
@@ -92,6 +93,10 @@ class SqGraphStagesDebug(C.Structure):
     _fields_ = [("n_keep", C.c_int32), ("keep", _PU8), ("depth_ambiguous", C.c_int32), ("fallback", C.c_int32), ("rc", C.c_int32)]
 
 
+class SqSegmentDebug(C.Structure):
+    _fields_ = [("n_seeds", C.c_int64), ("seeds3", _P32)] + [(k, C.c_int64) for k in ("stretches", "again", "longest", "sens", "extended", "kept_with_nodes", "flagged")] + [("fallback", C.c_int32)]
+
+
 class SquidError(RuntimeError):
     pass
 
@@ -136,6 +141,10 @@ def load_library() -> C.CDLL:
         lib.sq_bwa_nodes_on_device.argtypes = [C.c_void_p, C.c_int32]
         lib.sq_debug_bwa_seed_nodes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqBwaNodesDebug)]
         lib.sq_debug_bwa_seed_nodes_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _P32, C.POINTER(C.c_uint32), _P32, C.POINTER(SqBwaNodesDebug)]
+        lib.sq_segment_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_debug_segment_seeds.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqSegmentDebug)]
+        lib.sq_debug_segment_seeds_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _P32, C.c_int32, _P32, C.c_int32, _P32, C.c_int32, _P32, _P32, _P32, _P32, C.c_int32, _P32,
+                                                      C.POINTER(SqSegmentDebug)]
         lib.sq_clear_records.argtypes = [C.c_void_p]
         lib.sq_release_reader_buffers.argtypes = [C.c_void_p]
         lib.sq_set_source.argtypes = [C.c_void_p, C.c_char_p]
@@ -286,6 +295,46 @@ class Context:
         """sq_bwa_edges_on_device: a --bwa context also runs the record loop of RawEdges over its batch in HBM (it implies bwa_on_device; same
         results; off by default; any other context ignores it)"""
         self._chk(self.lib.sq_bwa_edges_on_device(self.h, 1 if on else 0), "sq_bwa_edges_on_device")
+
+    def segment_on_device(self, on: bool = True):
+        """sq_segment_on_device: the segmentation automaton of BuildNode_STAR as a kernel, one wave per active stretch, with the host's walk over
+        the reports (same results; off by default; a --bwa context ignores it and a sharded one keeps the host replay)"""
+        self._chk(self.lib.sq_segment_on_device(self.h, 1 if on else 0), "sq_segment_on_device")
+
+    @staticmethod
+    def _segment_result(d) -> dict:
+        import numpy as np
+
+        seeds = np.ctypeslib.as_array(d.seeds3, shape=(3 * d.n_seeds,)).reshape(-1, 3).tolist() if d.n_seeds else []
+        return {"seeds": [tuple(x) for x in seeds], "stretches": int(d.stretches), "again": int(d.again), "longest": int(d.longest), "sens": int(d.sens), "extended": int(d.extended),
+                "kept_with_nodes": int(d.kept_with_nodes), "flagged": int(d.flagged), "fallback": int(d.fallback)}
+
+    def debug_segment_seeds(self, route: int = 1) -> dict:
+        """sq_debug_segment_seeds (tests): the segmentation automaton alone over the context's records and fragments, route 0 = the host automaton
+        in one go, 1 = the kernel plus the host walk.  seeds: [(chr, pos, len)] in order; stretches, again, longest, sens, extended,
+        kept_with_nodes, flagged, fallback"""
+        d = SqSegmentDebug()
+        self._chk(self.lib.sq_debug_segment_seeds(self.h, route, C.byref(d)), "sq_debug_segment_seeds")
+        return self._segment_result(d)
+
+    def debug_segment_seeds_tables(self, read_len, recs6, disc4, part2, rest_off, rest_pos, rest_len, trigger, zero3, route: int = 1) -> dict:
+        """sq_debug_segment_seeds_tables (tests): the same on the automaton's inputs as plain arrays (see include/squid_hip.h); the number of
+        clusters is len(trigger)"""
+        import numpy as np
+
+        def arr(x, w):
+            a = np.ascontiguousarray(np.asarray(x, dtype=np.int32).reshape(-1))
+            assert len(a) % w == 0
+            return a
+
+        r6, d4, p2, z3 = arr(recs6, 6), arr(disc4, 4), arr(part2, 2), arr(zero3, 3)
+        ro, rp, rl, tr = arr(rest_off, 1), arr(rest_pos, 1), arr(rest_len, 1), arr(trigger, 1)
+        assert len(ro) == len(tr) + 1 and int(ro[-1]) == len(rp) == len(rl)
+        P = lambda a: a.ctypes.data_as(_P32)
+        d = SqSegmentDebug()
+        self._chk(self.lib.sq_debug_segment_seeds_tables(self.h, route, read_len, len(r6) // 6, P(r6), len(d4) // 4, P(d4), len(p2) // 2, P(p2), len(tr), P(ro), P(rp), P(rl), P(tr), len(z3) // 3, P(z3),
+                                                         C.byref(d)), "sq_debug_segment_seeds_tables")
+        return self._segment_result(d)
 
     def bwa_nodes_on_device(self, on: bool = True):
         """sq_bwa_nodes_on_device: a --bwa context also runs the record automaton of BuildNode_BWA (the seed nodes) over its batch in HBM (it implies

@@ -314,7 +314,21 @@ static int build_graph(sq_ctx* c) {
             if (rc) return rc;
         }
         c->counts.n_break = g.n_break;
-        {
+        bool seg_on_device = false;
+        if (c->seg_dev_on()) {  // (sq_segment_on_device: one wave per stretch, the host walks the reports; a plan too large comes back)
+            SegWalk W;
+            bool fb = false;
+            c->timer.add("segment_device_fallback", 0, 0, 0);
+            rc = segment_replay_device(c, *g.plan, g.seeds, W, fb);
+            if (rc) return rc;
+            if (fb) c->timer.add("segment_device_fallback", 0, 0, 1);
+            else {
+                seg_on_device = true;
+                c->timer.add("segment_stretches", 0, 0, W.stretches); c->timer.add("segment_stretches_run_again", 0, 0, W.again); c->timer.add("segment_longest_stretch", 0, 0, W.longest);
+                g.seedsA = g.seeds; g.seedsB.clear(); g.sensB.clear(); g.hasC = false;
+            }
+        }
+        if (!seg_on_device) {
             HostClock hc(c, "host_segment_replay");
             g.seedsB.clear(); g.sensB.clear(); g.hasC = false;
             std::future<int> hypB;  // a shard that does not start the stream replays under both pasts, side by side
@@ -851,6 +865,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     if (env_set("SQUID_CHIM_STAGES_GPU")) c->chim_dev_env = env_nonzero("SQUID_CHIM_STAGES_GPU") ? 1 : 0;  // forces / forbids the device route of the chimeric graph stages
     if (env_set("SQUID_BWA_STAGES_GPU")) c->bwa_dev_env = env_nonzero("SQUID_BWA_STAGES_GPU") ? 1 : 0;    // the same for node depth / breakpoint support of a --bwa context
     if (env_set("SQUID_BWA_EDGES_GPU")) c->bwa_edges_env = env_nonzero("SQUID_BWA_EDGES_GPU") ? 1 : 0;    // the same for the BAM loop of RawEdges of a --bwa context
+    if (env_set("SQUID_SEGMENT_GPU")) c->seg_dev_env = env_nonzero("SQUID_SEGMENT_GPU") ? 1 : 0;          // the same for BuildNode_STAR's segmentation automaton (not --bwa, not sharded)
     if (env_set("SQUID_BWA_NODES_GPU")) c->bwa_nodes_env = env_nonzero("SQUID_BWA_NODES_GPU") ? 1 : 0;    // the same for the record automaton of BuildNode_BWA of a --bwa context
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
@@ -1530,6 +1545,59 @@ int sq_bwa_edges_on_device(sq_ctx* c, int32_t on) {
     if (!c) return SQ_E_ARG;
     c->bwa_edges_asked = on != 0;  // (only a --bwa context looks at it: bwa_edges_on)
     return SQ_OK;
+}
+int sq_segment_on_device(sq_ctx* c, int32_t on) {
+    if (!c) return SQ_E_ARG;
+    c->seg_dev_asked = on != 0;  // (a --bwa context and a sharded one keep their host routes: seg_dev_on)
+    return SQ_OK;
+}
+static int segment_debug_view(sq_ctx* c, SegPlan& plan, int read_len, int32_t route, sq_segment_debug* out) {
+    static thread_local SegSeedsDebug R;
+    std::memset(out, 0, sizeof *out);
+    const int rc = segment_seeds_debug(c, plan, read_len, route, nullptr, R);
+    dev_flush_timers(c);
+    if (rc) return rc;
+    out->n_seeds = (int64_t)R.seeds3.size() / 3; out->seeds3 = R.seeds3.data();
+    out->stretches = R.walk.stretches; out->again = R.walk.again; out->longest = R.walk.longest; out->sens = R.walk.sens; out->extended = R.walk.extended;
+    out->kept_with_nodes = R.walk.kept_with_nodes; out->flagged = R.walk.flagged; out->fallback = R.fallback ? 1 : 0;
+    return SQ_OK;
+}
+int sq_debug_segment_seeds(sq_ctx* c, int32_t route, sq_segment_debug* out) {
+    if (!c || !out || (route != 0 && route != 1)) return SQ_E_ARG;
+    return abi_guard(c, "sq_debug_segment_seeds", [&]() -> int {
+        if (c->bwa) return fail(c, SQ_E_ARG, "sq_debug_segment_seeds needs a STAR context");
+        std::shared_ptr<SegPlan> plan;
+        const int rc = segment_plan_of_context(c, plan);
+        if (rc) return rc;
+        return segment_debug_view(c, *plan, 0, route, out);
+    });
+}
+int sq_debug_segment_seeds_tables(sq_ctx* c, int32_t route, int32_t read_len, int64_t n_recs, const int32_t* recs6, int32_t n_disc, const int32_t* disc4, int32_t n_part, const int32_t* part2,
+                                  int32_t n_clusters, const int32_t* rest_off, const int32_t* rest_pos, const int32_t* rest_len, const int32_t* trigger, int32_t n_zero, const int32_t* zero3,
+                                  sq_segment_debug* out) {
+    if (!c || !out || (route != 0 && route != 1) || read_len <= 0 || n_recs < 0 || n_disc < 0 || n_part < 0 || n_clusters < 0 || n_zero < 0 || (n_recs && !recs6) || (n_disc && !disc4) || (n_part && !part2) || !rest_off ||
+        (n_clusters && !trigger) || (n_zero && !zero3))
+        return SQ_E_ARG;
+    return abi_guard(c, "sq_debug_segment_seeds_tables", [&]() -> int {
+        std::vector<int32_t> cl4;
+        segment_clusters_of_tables(read_len, n_disc, disc4, cl4);
+        if ((int64_t)cl4.size() != 4 * (int64_t)n_clusters) return fail(c, SQ_E_ARG, "sq_debug_segment_seeds_tables: the blocks make " + std::to_string(cl4.size() / 4) + " clusters, not n_clusters");
+        if (rest_off[n_clusters] && (!rest_pos || !rest_len)) return SQ_E_ARG;
+        std::vector<StreamRec> recs((size_t)n_recs);
+        for (int64_t i = 0; i < n_recs; ++i) {
+            const int32_t* q = recs6 + 6 * i;
+            StreamRec r{};
+            r.refid = q[0]; r.pos = q[1]; r.fb_refpos = q[2]; r.fb_matchref = q[3]; r.fb_readpos = (uint16_t)q[4]; r.flags = (uint8_t)q[5];
+            recs[(size_t)i] = r;
+        }
+        SegTablesIn in;
+        in.read_len = read_len; in.n_recs = n_recs; in.recs = recs.data(); in.n_disc = n_disc; in.disc4 = disc4; in.n_part = n_part; in.part2 = part2;
+        in.rest_off = rest_off; in.rest_pos = rest_pos; in.rest_len = rest_len; in.trigger = trigger; in.n_zero = n_zero; in.zero3 = zero3;
+        std::shared_ptr<SegPlan> plan;
+        const int rc = segment_plan_from_tables(c, in, plan);
+        if (rc) return rc;
+        return segment_debug_view(c, *plan, read_len, route, out);
+    });
 }
 int sq_bwa_nodes_on_device(sq_ctx* c, int32_t on) {
     if (!c) return SQ_E_ARG;

@@ -284,6 +284,11 @@ struct sq_ctx {
     bool chim_s1_device = false;      // this graph's RawEdgesChim ran on the device: c->frags is untrimmed, the trimmed blocks are in HBM
     bool chim_s2_pending = false;     // ExactBreakpoint is queued on the stream (dev_exact_breakpoints_start); sq_call_sv collects it
     bool chim_dev_on() const { return !bwa && (chim_dev_env >= 0 ? chim_dev_env != 0 : chim_dev_asked); }
+    // BuildNode_STAR's segmentation automaton on the device (sq_segment_on_device; SQUID_SEGMENT_GPU=1 / =0, read by sq_create, forces / forbids it).
+    // A --bwa context has no such automaton and a chromosome-sharded one keeps the host replay (its hypotheses A/B/C are host work)
+    bool seg_dev_asked = false;
+    int seg_dev_env = -1;
+    bool seg_dev_on() const { return !bwa && !shard.on && (seg_dev_env >= 0 ? seg_dev_env != 0 : seg_dev_asked); }
     // --bwa: node depth and breakpoint support on the device (sq_bwa_on_device; SQUID_BWA_STAGES_GPU=1 / =0, read by sq_create, forces / forbids it)
     bool bwa_dev_asked = false;       // what the call said
     int bwa_dev_env = -1;             // the override: -1 none
@@ -449,6 +454,47 @@ int segment_prepare(sq_ctx* c, SegPlan& plan, int64_t& n_break);
 // `seed`: the real last node emitted before this shard (it may get extended: the result then starts with it)
 int segment_replay(sq_ctx* c, SegPlan& plan, std::vector<Node>& seeds, bool virtual_back, std::vector<int32_t>* sens, const Node* seed);
 int tile_genome(sq_ctx* c, std::vector<Node>& seeds, std::vector<Node>& out);
+// -- the automaton on the device (sq_segment_on_device; kernels: sq_segment_stage.inc, host entry: dev_segment_run in sq_kernels.hip)
+// what the kernels read, as flat tables (segment_device_tables makes them from a prepared plan): d4 = nd + 1 blocks (refid, refpos, matchref, rev),
+// part2 = PartAlignPos, cl4 = (ds, de, chr, right) per cluster, the ConcordRest CSR, the triggers, one sgs::STRETCH row per active stretch
+struct SegDevTables {
+    int32_t RL = 0, nd = 0, ncl = 0, npart = 0, na = 0, K_eff = 0;
+    std::vector<int32_t> d4, part2, cl4, rest_off, rest_pos, rest_len, trigger, stretch;
+    int64_t n_recs = 0, node_slots = 0, longest = 0;
+    const StreamRec* recs = nullptr;  // the host copy of the summaries (the device keeps its own: DeviceRecords::srec)
+};
+// report: na rows of sgs::REPORT values; nodes3: node_slots nodes (chr, pos, len), a stretch's slice starts at its S_NODE_OFF
+struct SegDevOut { std::vector<int32_t> report, nodes3; };
+enum { SGR_FLAGS = 0, SGR_NODES, SGR_MINCHR, SGR_BOUND, SGR_NSENS, SGR_SENS, SGR_EXT = SGR_SENS + 4, SGR_CLUSTERS = SGR_EXT + 3, SGR_SUBS, SGR_MMAX, SGR_SPARE, SGR_ROW };  // (sgs::R_*)
+enum { SGF_CONSULTED = 1, SGF_EXIST = 2, SGF_M_FULL = 4, SGF_CAPACITY = 4 | 8 | 16 | 32 };                                                                             // (sgs::F_*)
+enum { SGT_LO = 0, SGT_HI, SGT_KC, SGT_SHIFT, SGT_OCHR, SGT_ORIGHT, SGT_NODE_OFF, SGT_NODE_CAP, SGT_ROW };                                                             // (sgs::S_*)
+struct SegWalk { int64_t stretches = 0, again = 0, longest = 0, kept_with_nodes = 0, sens = 0, extended = 0, ext[3] = {0, 0, 0}, flagged = 0, flagged_margins = 0, sens_hits = 0, leading_kept = 0; };
+// null: the plan is too large for the route's tables (the caller takes segment_replay)
+const SegDevTables* segment_device_tables(const sq_ctx* c, SegPlan& plan);
+// recs_on_device: DeviceRecords::srec already holds T.recs (dev_fetch_stream made them there); else they are uploaded.  static_key: the
+// tables that only change with the chimeric fragments are uploaded when it differs from the key of the last upload (0: always)
+int dev_segment_run(sq_ctx* c, const SegDevTables& T, bool recs_on_device, uint64_t static_key, SegDevOut& out, bool& fallback);
+bool dev_segment_recs_resident(const sq_ctx* c, int64_t n_recs);  // the last dev_fetch_stream left exactly these summaries in HBM
+// the host's walk over the stretch reports in order with the real last node; a stretch whose report does not hold behind that node, or
+// that hit a capacity, is run again with replay_range behind exactly that node (also tools/segment_emu.cpp, over emulated reports)
+int segment_walk(sq_ctx* c, SegPlan& plan, const SegDevTables& T, const SegDevOut& D, std::vector<Node>& seeds, SegWalk& W);
+// the device route in place of segment_replay (no shard): fallback = the plan went back to the caller
+int segment_replay_device(sq_ctx* c, SegPlan& plan, std::vector<Node>& seeds, SegWalk& W, bool& fallback);
+// sq_debug_segment_seeds(_tables): route 0 = replay_range in one go, serial; 1 = the kernels plus the walk
+struct SegSeedsDebug { std::vector<int32_t> seeds3; SegWalk walk; bool fallback = false; };
+struct SegTablesIn {  // the automaton's inputs as plain arrays (sq_debug_segment_seeds_tables, tools/segment_emu.cpp)
+    int32_t read_len = 0;
+    int64_t n_recs = 0; const StreamRec* recs = nullptr;       // the whole kept stream
+    int32_t n_disc = 0; const int32_t* disc4 = nullptr;        // sorted discordant blocks: refid, refpos, matchref, rev
+    int32_t n_part = 0; const int32_t* part2 = nullptr;        // sorted PartAlignPos
+    const int32_t *rest_off = nullptr, *rest_pos = nullptr, *rest_len = nullptr;  // ConcordRest CSR over the clusters build_clusters makes
+    const int32_t* trigger = nullptr;                           // per cluster
+    int32_t n_zero = 0; const int32_t* zero3 = nullptr;        // zero-coverage records: kept index, otherChr, otherright in front of it
+};
+int segment_clusters_of_tables(int read_len, int32_t n_disc, const int32_t* disc4, std::vector<int32_t>& cl4);  // build_clusters on a block table: (ds, de, chr, right)
+int segment_plan_from_tables(sq_ctx* c, const SegTablesIn& in, std::shared_ptr<SegPlan>& plan);
+int segment_plan_of_context(sq_ctx* c, std::shared_ptr<SegPlan>& plan);  // clusters + scan + prepare over the context's own records and fragments
+int segment_seeds_debug(sq_ctx* c, SegPlan& plan, int read_len, int route, const SegDevOut* emulated, SegSeedsDebug& out);
 
 // ---- sq_graph.cpp
 struct Located { std::vector<int> node; };

@@ -38,6 +38,7 @@
 #include "sq_bwa_stage.inc"
 #include "sq_bwa_edges.inc"
 #include "sq_bwa_nodes.inc"
+#include "sq_segment_stage.inc"
 
 #define HIPCHK(call)                                                                                         \
     do {                                                                                                     \
@@ -230,6 +231,11 @@ struct DeviceRecords {
     DBuf<int32_t> prev1, prev2, rank1, restoff, scratch_a, scratch_b, scratch_c, spine;
     DBuf<int32_t> part_prev, part_next, b0_a, b0_b, b0_home, fc_seg;
     DBuf<StreamRec> srec;
+    int64_t srec_n = -1;  // summaries the last dev_fetch_stream left in srec (-1: not what the host copy holds)
+    // sq_segment_on_device (sq_segment_stage.inc): blocks | clip positions | cluster table (kept while seg_key names the plan); ConcordRest CSR |
+    // triggers | stretch rows; report rows | node slices
+    DBuf<int32_t> seg_static, seg_pass, seg_out;
+    uint64_t seg_key = 0;
     DBuf<int32_t> rest_refpos, rest_matchref;
     // node table
     DBuf<int32_t> n_chr, n_bucket;  // n_chr: packed node table chr | pos | len | chr_start | bucket_off | fine_off; n_bucket: the fine index
@@ -3099,6 +3105,7 @@ void dev_destroy(sq_ctx* c) {
     D.scratch_a.release(); D.scratch_b.release(); D.scratch_c.release(); D.spine.release();
     D.part_prev.release(); D.part_next.release(); D.b0_a.release(); D.b0_b.release(); D.b0_home.release(); D.fc_seg.release();
     D.srec.release(); D.rest_refpos.release(); D.rest_matchref.release();
+    D.seg_static.release(); D.seg_pass.release(); D.seg_out.release(); D.seg_key = 0; D.srec_n = -1;
     D.n_chr.release(); D.n_bucket.release();
     D.acc_a.release(); D.acc_b.release(); D.acc_c.release();
     D.h_key.release(); D.h_val.release(); D.flags.release(); D.bam_chunk.release(); D.bam_off.release(); D.chim_hash.release(); D.chim_off.release(); D.chim_len.release(); D.chim_blob.release(); D.chim_dead.release(); D.chim_slot_of.release(); D.chim_in_off.release(); D.chim_in_len.release(); D.parse_nblk.release(); D.parse_rel.release(); D.parse_first2.release();
@@ -4506,6 +4513,7 @@ int dev_fetch_stream(sq_ctx* c, const std::vector<std::pair<int64_t, int64_t>>& 
     const int nr = (int)ranges.size();
     range_off.assign(nr, 0);
     compact = nullptr;
+    D.srec_n = -1;
     if (!nr) return SQ_OK;
     static_assert(sizeof(StreamRec) == 24, "StreamRec is six words");
     const std::vector<int32_t>& TR = D.h_tile_rank;
@@ -4545,6 +4553,7 @@ int dev_fetch_stream(sq_ctx* c, const std::vector<std::pair<int64_t, int64_t>>& 
         HIPCHK(hipStreamSynchronize(s));  // (items goes out of scope)
     }
     for (const auto& pt : patch) dst[pt.second] = *term;
+    if (patch.empty() && !items.empty()) D.srec_n = (int64_t)total;
     compact = dst;
     c->timer.add("d2h_stream_summary", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), 0);
     return SQ_OK;
@@ -5589,6 +5598,77 @@ int dev_bwa_seed_nodes(sq_ctx* c, int read_len, const int32_t rl5[5], BwaNodesOu
       HIPCHK(hipMemcpyAsync(out.dis_in.data(), dis_in, (size_t)np * 4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(out.report.data(), report, (size_t)np * BNR_ROW * 4, hipMemcpyDeviceToHost, s));
       if (total) HIPCHK(hipMemcpyAsync(out.seeds3.data(), strung, 3 * (size_t)total * 4, hipMemcpyDeviceToHost, s)); }
+    HIPCHK(hipStreamSynchronize(s));
+    return SQ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ BuildNode_STAR's segmentation automaton on the device
+// (sq_segment_on_device; the kernel's body is in sq_segment_stage.inc)
+__global__ __launch_bounds__(256) void k_seg_run(sgs::Tab X, int32_t* nodes, int32_t* report) {
+    __shared__ uint32_t margins[4][sgs::M_CAP];
+    const int a = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);  // one wave per active stretch
+    if (a >= X.na) return;
+    sgs::run_stretch(X, (wv::lds_u32*)margins[threadIdx.x >> 6], nodes, report, a);
+}
+static_assert(sizeof(sgs::Rec) == sizeof(StreamRec) && offsetof(sgs::Rec, flags) == offsetof(StreamRec, flags) && offsetof(sgs::Rec, fb_readpos) == offsetof(StreamRec, fb_readpos), "sgs::Rec is StreamRec");
+static_assert(sgs::W_CONC == SR_CONC && sgs::W_PART == SR_PART && sgs::W_REV == SR_REV, "sq_segment_stage.inc restates these");
+static_assert((int)sgs::REPORT == (int)SGR_ROW && (int)sgs::R_EXT == (int)SGR_EXT && (int)sgs::R_SENS == (int)SGR_SENS && (int)sgs::R_MMAX == (int)SGR_MMAX && (int)sgs::SENS_CAP == 4 && (int)sgs::STRETCH == (int)SGT_ROW &&
+              (int)sgs::S_NODE_CAP == (int)SGT_NODE_CAP && (int)sgs::F_EXIST == (int)SGF_EXIST && (int)sgs::F_CAPACITY == (int)SGF_CAPACITY && (int)sgs::F_M_FULL == (int)SGF_M_FULL, "the rows of sq_segment_stage.inc as sq_segment.cpp reads them");
+
+bool dev_segment_recs_resident(const sq_ctx* c, int64_t n_recs) { return c->dev && n_recs > 0 && c->dev->srec_n == n_recs; }
+
+// One wave per active stretch over the tables of a prepared plan.  fallback: nothing of `out` is valid and the caller takes segment_replay
+// (a device buffer could not be had).
+int dev_segment_run(sq_ctx* c, const SegDevTables& T, bool recs_on_device, uint64_t static_key, SegDevOut& out, bool& fallback) {
+    out = SegDevOut();
+    fallback = false;
+    if (!c->dev) { fallback = true; return SQ_OK; }
+    HIPCHK(hipSetDevice(c->P.device));
+    DeviceRecords& D = *c->dev;
+    hipStream_t s = c->stream;
+    const size_t na = (size_t)T.na, ncl = (size_t)T.ncl;
+    if (na == 0) return SQ_OK;
+    if (T.stretch.size() != na * SGT_ROW || T.d4.size() != 4 * ((size_t)T.nd + 1) || T.cl4.size() != 4 * ncl || T.part2.size() != 2 * (size_t)T.npart || T.rest_off.size() != ncl + 1 || T.trigger.size() != ncl ||
+        T.rest_pos.size() != T.rest_len.size() || (ncl && (size_t)T.rest_off[ncl] != T.rest_pos.size()) || !T.recs || T.n_recs <= 0)
+        return fail(c, SQ_E_ARG, "internal: the tables of the segmentation stage do not fit together");
+#define SEG_RESERVE(buf, count) do { if ((buf).reserve((size_t)(count)) != hipSuccess) { (void)hipGetLastError(); fallback = true; return SQ_OK; } } while (0)
+    const size_t n_static = T.d4.size() + T.part2.size() + T.cl4.size() + 4;
+    const size_t n_rest = T.rest_pos.size();
+    const size_t n_pass = (ncl + 1) + 2 * n_rest + ncl + na * SGT_ROW + 4;
+    const size_t n_out = na * SGR_ROW + 3 * (size_t)T.node_slots + 4;
+    const bool have_static = static_key != 0 && D.seg_key == static_key && D.seg_static.p && D.seg_static.cap >= n_static;
+    if (!have_static) { D.seg_key = 0; SEG_RESERVE(D.seg_static, n_static); }
+    SEG_RESERVE(D.seg_pass, n_pass); SEG_RESERVE(D.seg_out, n_out);
+    if (!recs_on_device) { D.srec_n = -1; SEG_RESERVE(D.srec, T.n_recs); }
+#undef SEG_RESERVE
+    int32_t *d4 = D.seg_static.p, *part2 = d4 + T.d4.size(), *cl4 = part2 + T.part2.size();
+    int32_t *rest_off = D.seg_pass.p, *rest_pos = rest_off + ncl + 1, *rest_len = rest_pos + n_rest, *trigger = rest_len + n_rest, *stretch = trigger + ncl;
+    int32_t *report = D.seg_out.p, *nodes = report + na * SGR_ROW;
+    {
+        EvTimer t(c, "seg_upload", 4.0 * (have_static ? 0 : n_static) + 4.0 * n_pass + (recs_on_device ? 0.0 : 24.0 * T.n_recs));
+        if (!have_static) {
+            HIPCHK(hipMemcpyAsync(d4, T.d4.data(), T.d4.size() * 4, hipMemcpyHostToDevice, s));
+            if (!T.part2.empty()) HIPCHK(hipMemcpyAsync(part2, T.part2.data(), T.part2.size() * 4, hipMemcpyHostToDevice, s));
+            if (ncl) HIPCHK(hipMemcpyAsync(cl4, T.cl4.data(), T.cl4.size() * 4, hipMemcpyHostToDevice, s));
+        }
+        HIPCHK(hipMemcpyAsync(rest_off, T.rest_off.data(), (ncl + 1) * 4, hipMemcpyHostToDevice, s));
+        if (n_rest) { HIPCHK(hipMemcpyAsync(rest_pos, T.rest_pos.data(), n_rest * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(rest_len, T.rest_len.data(), n_rest * 4, hipMemcpyHostToDevice, s)); }
+        if (ncl) HIPCHK(hipMemcpyAsync(trigger, T.trigger.data(), ncl * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(stretch, T.stretch.data(), na * SGT_ROW * 4, hipMemcpyHostToDevice, s));
+        if (!recs_on_device) HIPCHK(hipMemcpyAsync(D.srec.p, T.recs, (size_t)T.n_recs * sizeof(StreamRec), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));  // (the sources are pageable)
+    if (static_key != 0) D.seg_key = static_key;
+    sgs::Tab X;
+    X.recs = (const sgs::Rec*)D.srec.p; X.RL = T.RL; X.nd = T.nd; X.ncl = T.ncl; X.npart = T.npart; X.na = T.na; X.K_eff = T.K_eff;
+    X.d4 = d4; X.part2 = part2; X.cl4 = cl4; X.rest_off = rest_off; X.rest_pos = rest_pos; X.rest_len = rest_len; X.trigger = trigger; X.stretch = stretch;
+    { EvTimer t(c, "k_seg_run", 24.0 * T.n_recs + 16.0 * T.nd + 4.0 * n_out);
+      hipLaunchKernelGGL(k_seg_run, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, s, X, nodes, report); }
+    HIPCHK(hipGetLastError());
+    out.report.resize(na * SGR_ROW); out.nodes3.resize(3 * (size_t)T.node_slots);
+    { EvTimer t(c, "seg_download", 4.0 * (n_out - 4));
+      HIPCHK(hipMemcpyAsync(out.report.data(), report, na * SGR_ROW * 4, hipMemcpyDeviceToHost, s));
+      if (T.node_slots) HIPCHK(hipMemcpyAsync(out.nodes3.data(), nodes, 3 * (size_t)T.node_slots * 4, hipMemcpyDeviceToHost, s)); }
     HIPCHK(hipStreamSynchronize(s));
     return SQ_OK;
 }

@@ -175,6 +175,7 @@ struct Seg {
     int disChr = 0, otherChr = 0, nextdisChr = 0, disright = 0, otherright = 0, nextdisright = 0;
     int markStart = -1, markChr = -1;
     const bool recount = env_set("SQUID_REPLAY_CHECK");  // (tests: every candidate counted twice, check_candidate)
+    long long n_ext[3] = {0, 0, 0};  // out.back().len += ... by place: the disCount rule, the flush of the second window advance, the zero-coverage rule
 
     Seg(const sq_ctx* c, const StreamRec* recs, const SegStatic& st, std::vector<Node>& out)
         : c(c), recs(recs), RL(c->read_len), D(st.D), nd(st.nd), part(st.part), clusters(st.clusters), st(st), out(out) {}
@@ -363,7 +364,7 @@ struct Seg {
             auto tC = tick();
             if (lastC != -1 && (!split || back_end() != lastC)) close_node(chr, curStart, curEnd, lastC, split);
             if (disStart != -1 && !split && disCount > std::min(5.0, 4.0 * (disEnd - disStart) / RL)) {  // :518-527 (FP64 as in the reference)
-                if (have_back() && out.back().chr == D[de - 1].refid && disEnd - back_end() < NEAR) out.back().len += disEnd - back_end();
+                if (have_back() && out.back().chr == D[de - 1].refid && disEnd - back_end() < NEAR) { out.back().len += disEnd - back_end(); ++n_ext[0]; }
                 else push_node(D[de - 1].refid, disStart, disEnd - disStart);
                 curStart = disEnd; curEnd = disEnd;
                 markStart = disEnd; markChr = chr;
@@ -398,7 +399,7 @@ struct Seg {
                 if (!cfree) { El b = el(cw[co]); cfree = b.refid != markChr || b.refpos > zero + RL; }
                 if (!pfree) { El b = el(pw[po]); pfree = b.refid != markChr || b.refpos > zero; }
                 if (markStart != -1 && (recChr > markChr || recPos > zero + RL) && cfree && pfree) {
-                    if (zero > markStart && zero < markStart + NEAR && have_back() && out.back().chr == markChr) out.back().len += zero - back_end();
+                    if (zero > markStart && zero < markStart + NEAR && have_back() && out.back().chr == markChr) { out.back().len += zero - back_end(); ++n_ext[1]; }
                     else if (zero > markStart) push_node(markChr, markStart, zero - markStart);
                     curStart = zero;
                     markChr = -1; markStart = -1;
@@ -429,12 +430,20 @@ struct SegPlan {
     std::vector<int32_t> cl_chr, cl_start, cl_right;  // the cluster table as uploaded
     long long other_max_local = INT64_MIN;  // running (otherChr, otherrightmost) pair over the whole local stream
     bool skip_first = false;  // the local stream does not start the global one: its first record only opens a stretch
+    int64_t n_compact = 0;    // summaries in `compact`
+    // sq_segment_on_device: the flat tables the kernels read (the static ones are made once per plan: `serial` names the plan on the device)
+    uint64_t serial = 0;
+    bool dev_static_made = false;
+    SegDevTables dev;
+    std::vector<StreamRec> own_recs;  // segment_plan_from_tables: the caller's stream
 };
+static std::atomic<uint64_t> plan_serial{0};
 
 // static part: discordant blocks, clip positions, cluster table; stream scans that need nothing from other shards
 // (host only, reads the chimeric fragments: may run next to the record kernels) returns the elapsed milliseconds
 double segment_clusters(const sq_ctx* c, std::shared_ptr<SegPlan>& plan, std::vector<Blk>& disc_sorted) {
     plan = std::make_shared<SegPlan>();
+    plan->serial = ++plan_serial;
     SegStatic& S = plan->st;
     const auto t_begin = std::chrono::steady_clock::now();
     static const bool laps = env_set("SQUID_PREP_DEBUG");
@@ -658,7 +667,7 @@ int segment_prepare(sq_ctx* c, SegPlan& P, int64_t& n_break) {
         else n_break = std::min<int64_t>(K, (int64_t)sup.trigger[ncl - 1] + 2);
     } else n_break = std::max<int64_t>(0, std::min<int64_t>(K, sh.n_break_global - sh.kept_before));
     // (the plan object is kept across passes, sq_capi.cpp: every per-pass field is put back before the early way out)
-    P.active.clear(); P.first_cluster.clear(); P.shift.clear(); P.compact = nullptr; P.skip_first = false; P.k0 = 0;
+    P.active.clear(); P.first_cluster.clear(); P.shift.clear(); P.compact = nullptr; P.skip_first = false; P.k0 = 0; P.n_compact = 0;
     if (nd == 0 || K == 0) return SQ_OK;
 
     // ---- stretches between zero-coverage records; a stretch j covers: the push step of its first record lo (a
@@ -696,6 +705,7 @@ int segment_prepare(sq_ctx* c, SegPlan& P, int64_t& n_break) {
     std::vector<int64_t> range_off;
     rc = dev_fetch_stream(c, ranges, P.compact, range_off, term ? &term_rec : nullptr);
     if (rc) return rc;
+    for (const auto& r : ranges) P.n_compact += r.second - r.first;
     P.shift.resize(active.size());
     for (size_t a = 0; a < active.size(); ++a) P.shift[a] = ranges[range_of[a]].first - range_off[range_of[a]];
     return SQ_OK;
@@ -706,7 +716,7 @@ int segment_prepare(sq_ctx* c, SegPlan& P, int64_t& n_break) {
 // on an earlier chromosome than anything the range looks at (then only its existence matters); `sens` collects the
 // pending node starts that were compared with that node's end without a chromosome test (SegmentGraph.cpp:623).
 static int replay_range(sq_ctx* c, SegPlan& plan, size_t a_begin, size_t a_end, std::vector<Node>& seeds, bool virtual_back, std::vector<int32_t>* sens, std::string& err,
-                        const Node* seed = nullptr) {
+                        const Node* seed = nullptr, long long* ext3 = nullptr, bool jump = false) {
     seeds.clear();
     std::vector<Node> sink;
     if (seed) sink.push_back(*seed);  // the real node in front (the result keeps it, possibly extended)
@@ -768,7 +778,7 @@ static int replay_range(sq_ctx* c, SegPlan& plan, size_t a_begin, size_t a_end, 
             // the first test compares with the end of the last node WITHOUT looking at its chromosome: if that node came from
             // an earlier shard the caller must check the recorded value against its real end
             if (sens && virtual_back && sink.size() == 1 && curChr == S.markChr && curRight > S.markStart && curRight - S.markStart < Seg::NEAR) sens->push_back(S.markStart);
-            if (curChr == S.markChr && curRight > S.markStart && curRight - S.markStart < Seg::NEAR && S.have_back() && S.markStart == S.back_end()) S.out.back().len += curRight - S.markStart;
+            if (curChr == S.markChr && curRight > S.markStart && curRight - S.markStart < Seg::NEAR && S.have_back() && S.markStart == S.back_end()) { S.out.back().len += curRight - S.markStart; ++S.n_ext[2]; }
             else if (curChr == S.markChr && curRight > S.markStart && curRight - S.markStart >= Seg::NEAR) S.push_node(S.markChr, S.markStart, curRight - S.markStart);
             S.markStart = -1; S.markChr = -1;
         }
@@ -778,9 +788,21 @@ static int replay_range(sq_ctx* c, SegPlan& plan, size_t a_begin, size_t a_end, 
     };
     const int ncl = (int)S.clusters.size();
     const auto t_begin = std::chrono::steady_clock::now();
+    if (jump && plan.first_cluster[a_begin] > 0) {
+        // (segment_walk runs single stretches again: the clusters consumed in front leave nothing but the right end of the last of them, and the
+        // pointer into the sorted clip positions only ever stands at or in front of the lower bound process_cluster advances it to)
+        const int fc = plan.first_cluster[a_begin];
+        S.kc = fc - 1; S.nextdisright = S.clusters[fc - 1].right; S.nextdisChr = S.clusters[fc - 1].chr;
+        const Blk& b0 = D[S.clusters[fc].ds];
+        size_t lo = 0, hi = S.part.size();
+        while (lo < hi) { const size_t m = lo + (hi - lo) / 2; if (S.part[m].first < b0.refid || (S.part[m].first == b0.refid && S.part[m].second + RL < b0.refpos)) lo = m + 1; else hi = m; }
+        S.ps = lo;
+        S.new_cluster();
+    } else {
     S.new_cluster();  // the reference does this at its first kept record (:341)
     // clusters consumed before this range (by earlier stretches, or by the closing record of an earlier shard)
     for (int k = 0; k < plan.first_cluster[a_begin]; ++k) S.new_cluster();
+    }
     for (size_t a = a_begin; a < a_end; ++a) {
         const int j = active[a];
         S.shift = plan.shift[a];
@@ -824,6 +846,7 @@ static int replay_range(sq_ctx* c, SegPlan& plan, size_t a_begin, size_t a_end, 
                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
     if (virtual_back) sink.erase(sink.begin());
     seeds = sink;
+    if (ext3) for (int k = 0; k < 3; ++k) ext3[k] += S.n_ext[k];
     return SQ_OK;
 }
 
@@ -890,6 +913,213 @@ int segment_replay(sq_ctx* c, SegPlan& plan, std::vector<Node>& seeds, bool virt
     if (!ok) { seeds.clear(); if (sens) sens->clear(); return sequential(); }
     for (size_t g = 0; g < ng; ++g) seeds.insert(seeds.end(), res[g].seeds.begin(), res[g].seeds.end());
     if (sens) *sens = up;
+    return SQ_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the automaton on the device (sq_segment_on_device)
+const SegDevTables* segment_device_tables(const sq_ctx* c, SegPlan& plan) {
+    const SegStatic& S = plan.st;
+    SegDevTables& T = plan.dev;
+    const size_t na = plan.active.size(), ncl = S.clusters.size();
+    if (plan.K_eff >= 0x7ffffff0ll || plan.n_compact >= 0x7ffffff0ll || (size_t)S.nd >= (1u << 29) || S.part.size() >= (1u << 30)) return nullptr;
+    T.RL = c->read_len; T.nd = S.nd; T.ncl = (int32_t)ncl; T.npart = (int32_t)S.part.size(); T.na = (int32_t)na; T.K_eff = (int32_t)plan.K_eff;
+    if (!plan.dev_static_made) {  // fixed by the chimeric fragments
+        T.d4.resize(4 * ((size_t)S.nd + 1));
+        for (size_t d = 0; d <= (size_t)S.nd; ++d) { const Blk& b = S.D[d]; T.d4[4 * d] = b.refid; T.d4[4 * d + 1] = b.refpos; T.d4[4 * d + 2] = b.matchref; T.d4[4 * d + 3] = b.rev ? 1 : 0; }
+        T.part2.resize(2 * S.part.size());
+        for (size_t q = 0; q < S.part.size(); ++q) { T.part2[2 * q] = S.part[q].first; T.part2[2 * q + 1] = S.part[q].second; }
+        T.cl4.resize(4 * ncl);
+        for (size_t k = 0; k < ncl; ++k) { const Cluster& cl = S.clusters[k]; T.cl4[4 * k] = cl.ds; T.cl4[4 * k + 1] = cl.de; T.cl4[4 * k + 2] = cl.chr; T.cl4[4 * k + 3] = cl.right; }
+        plan.dev_static_made = true;
+    }
+    T.rest_off = S.rest_off; T.rest_pos = S.rest_pos; T.rest_len = S.rest_len; T.trigger = plan.sup.trigger;
+    if (T.rest_off.size() != ncl + 1) T.rest_off.assign(ncl + 1, 0);
+    const std::vector<int32_t>& Z = plan.sup.zidx;
+    const int nz = (int)Z.size();
+    T.stretch.resize(na * SGT_ROW);
+    int64_t slots = 0;
+    T.longest = 0;
+    for (size_t a = 0; a < na; ++a) {
+        const int j = plan.active[a];
+        int32_t* r = T.stretch.data() + a * SGT_ROW;
+        const int64_t lo = j == 0 ? -1 : Z[j - 1], hi = j < nz ? Z[j] : plan.K_eff;
+        if (plan.shift[a] > INT32_MAX || plan.shift[a] < INT32_MIN) return nullptr;
+        // a cluster seldom emits more than a node or two: four per cluster the stretch consumes, and four more
+        const int64_t kn = a + 1 < na ? plan.first_cluster[a + 1] : (int64_t)ncl;
+        const int64_t cap = 4 * (kn - plan.first_cluster[a]) + 4;
+        r[SGT_LO] = (int32_t)lo; r[SGT_HI] = (int32_t)hi; r[SGT_KC] = plan.first_cluster[a]; r[SGT_SHIFT] = (int32_t)plan.shift[a];
+        r[SGT_OCHR] = j < nz ? plan.sup.z_ochr[j] : 0; r[SGT_ORIGHT] = j < nz ? plan.sup.z_oright[j] : 0;
+        if (slots + cap >= 0x20000000ll) return nullptr;
+        r[SGT_NODE_OFF] = (int32_t)slots; r[SGT_NODE_CAP] = (int32_t)cap;
+        slots += cap;
+        T.longest = std::max<int64_t>(T.longest, hi - lo);
+    }
+    T.node_slots = slots;
+    T.recs = plan.compact; T.n_recs = plan.n_compact;
+    return &T;
+}
+
+int segment_walk(sq_ctx* c, SegPlan& plan, const SegDevTables& T, const SegDevOut& D, std::vector<Node>& seeds, SegWalk& W) {
+    seeds.clear();
+    W = SegWalk();
+    const size_t na = plan.active.size();
+    if ((size_t)T.na != na || D.report.size() != na * SGR_ROW) return fail(c, SQ_E_ARG, "internal: the stretch reports do not belong to the plan");
+    W.stretches = (int64_t)na; W.longest = T.longest;
+    std::string err;
+    std::vector<Node> tmp;
+    for (size_t a = 0; a < na; ++a) {
+        const int32_t* r = D.report.data() + a * SGR_ROW;
+        const int32_t* st = T.stretch.data() + a * SGT_ROW;
+        const int flags = r[SGR_FLAGS];
+        const bool have = !seeds.empty();
+        bool ok = !(flags & SGF_CAPACITY);
+        if (flags & SGF_CAPACITY) ++W.flagged;
+        if (flags & SGF_M_FULL) ++W.flagged_margins;
+        const int nsens = std::min(r[SGR_NSENS], 4);
+        if (ok && !have) ok = !(flags & SGF_EXIST);  // (without a node every other comparison comes out as the guess says)
+        else if (ok) {
+            const Node& b = seeds.back();
+            const int end = b.pos + b.len;
+            if (flags & SGF_CONSULTED) ok = b.chr < r[SGR_MINCHR] || (b.chr == r[SGR_MINCHR] && end <= r[SGR_BOUND]);
+            for (int k = 0; k < nsens; ++k) if (r[SGR_SENS + k] == end) { ok = false; ++W.sens_hits; }
+        }
+        if (ok) {
+            if (!have) ++W.leading_kept;  // (kept with no node in front: valid with and without one)
+            W.sens += nsens;
+            const int n = r[SGR_NODES];
+            if (n > st[SGT_NODE_CAP] || (size_t)(st[SGT_NODE_OFF] + n) * 3 > D.nodes3.size()) return fail(c, SQ_E_ARG, "internal: a stretch reports more nodes than its slice holds");
+            const int32_t* q = D.nodes3.data() + 3 * (size_t)st[SGT_NODE_OFF];
+            for (int i = 0; i < n; ++i) seeds.push_back(Node{q[3 * i], q[3 * i + 1], q[3 * i + 2], 0, 0.0});
+            if (n) ++W.kept_with_nodes;
+            for (int k = 0; k < 3; ++k) W.ext[k] += r[SGR_EXT + k];
+            continue;
+        }
+        ++W.again;
+        const Node last = have ? seeds.back() : Node{0, 0, 0, 0, 0.0};
+        long long ext3[3] = {0, 0, 0};
+        const int rc = replay_range(c, plan, a, a + 1, tmp, false, nullptr, err, have ? &last : nullptr, ext3, true);
+        if (rc) return fail(c, rc, err);
+        for (int k = 0; k < 3; ++k) W.ext[k] += ext3[k];
+        if (have) {
+            if (tmp.empty()) return fail(c, SQ_E_ARG, "internal: a stretch run again lost the node in front of it");
+            seeds.back() = tmp[0];
+            seeds.insert(seeds.end(), tmp.begin() + 1, tmp.end());
+        } else seeds.insert(seeds.end(), tmp.begin(), tmp.end());
+    }
+    W.extended = W.ext[0] + W.ext[1] + W.ext[2];
+    return SQ_OK;
+}
+
+int segment_replay_device(sq_ctx* c, SegPlan& plan, std::vector<Node>& seeds, SegWalk& W, bool& fallback) {
+    seeds.clear();
+    W = SegWalk();
+    fallback = false;
+    if (plan.active.empty()) return SQ_OK;
+    const SegDevTables* T = segment_device_tables(c, plan);
+    if (!T) { fallback = true; return SQ_OK; }
+    SegDevOut D;
+    int rc = dev_segment_run(c, *T, dev_segment_recs_resident(c, T->n_recs), plan.serial, D, fallback);
+    if (rc || fallback) return rc;
+    HostClock hc(c, "host_segment_walk");
+    return segment_walk(c, plan, *T, D, seeds, W);
+}
+
+int segment_clusters_of_tables(int read_len, int32_t n_disc, const int32_t* disc4, std::vector<int32_t>& cl4) {
+    SegStatic S;
+    for (int32_t d = 0; d < n_disc; ++d) S.D.push_back(Blk{disc4[4 * d], disc4[4 * d + 1], 0, disc4[4 * d + 2], 0, disc4[4 * d + 3] != 0, false});
+    S.nd = n_disc;
+    S.build_clusters(read_len);
+    cl4.clear();
+    for (const Cluster& k : S.clusters) { cl4.push_back(k.ds); cl4.push_back(k.de); cl4.push_back(k.chr); cl4.push_back(k.right); }
+    return SQ_OK;
+}
+
+int segment_plan_from_tables(sq_ctx* c, const SegTablesIn& in, std::shared_ptr<SegPlan>& plan) {
+    plan = std::make_shared<SegPlan>();
+    SegPlan& P = *plan;
+    P.serial = ++plan_serial;
+    SegStatic& S = P.st;
+    for (int32_t d = 0; d < in.n_disc; ++d) {
+        const int32_t* q = in.disc4 + 4 * (size_t)d;
+        if (d && (q[0] < q[-4] || (q[0] == q[-4] && q[1] < q[-3]))) return fail(c, SQ_E_ARG, "the discordant blocks must be sorted by (refid, refpos)");
+        S.D.push_back(Blk{q[0], q[1], 0, q[2], 0, q[3] != 0, false});
+    }
+    S.nd = in.n_disc;
+    for (int32_t q = 0; q < in.n_part; ++q) S.part.push_back(std::make_pair(in.part2[2 * q], in.part2[2 * q + 1]));
+    if (!std::is_sorted(S.part.begin(), S.part.end())) return fail(c, SQ_E_ARG, "the clip positions must be sorted");
+    S.build_clusters(in.read_len);
+    S.D.push_back(Blk{0, 0, 0, 0, 0, false, false});
+    const int ncl = (int)S.clusters.size();
+    S.rest_off.assign(in.rest_off, in.rest_off + ncl + 1);
+    if (S.rest_off[0] != 0) return fail(c, SQ_E_ARG, "rest_off must start at 0");
+    for (int k = 0; k < ncl; ++k) if (S.rest_off[k + 1] < S.rest_off[k]) return fail(c, SQ_E_ARG, "rest_off must not go down");
+    const size_t cnt = (size_t)S.rest_off[ncl];
+    S.rest_pos.assign(in.rest_pos, in.rest_pos + cnt); S.rest_len.assign(in.rest_len, in.rest_len + cnt);
+    S.rest_max.assign((size_t)ncl, 0);
+    for (int k = 0; k < ncl; ++k)
+        for (int i = S.rest_off[k]; i < S.rest_off[k + 1]; ++i) {
+            if (i > S.rest_off[k] && S.rest_pos[i] < S.rest_pos[i - 1]) return fail(c, SQ_E_ARG, "the ConcordRest candidates of a cluster must be sorted by refpos");
+            S.rest_max[k] = std::max(S.rest_max[k], S.rest_len[i]);
+        }
+    const int64_t K = in.n_recs;
+    if (K >= 0x7ffffff0ll) return fail(c, SQ_E_ARG, "more than 2^31 records");
+    P.own_recs.assign(in.recs, in.recs + K);
+    P.compact = P.own_recs.data(); P.n_compact = K;
+    P.K = P.K_eff = K;
+    SegSupport& sup = P.sup;
+    sup.trigger.assign(in.trigger, in.trigger + ncl);
+    for (int k = 0; k < ncl; ++k) if (sup.trigger[k] < 0 || (k && sup.trigger[k] < sup.trigger[k - 1])) return fail(c, SQ_E_ARG, "the triggers must be kept indices in ascending order");
+    for (int32_t z = 0; z < in.n_zero; ++z) {
+        const int32_t* q = in.zero3 + 3 * (size_t)z;
+        if (q[0] < 0 || q[0] >= K || (z && q[0] <= q[-3])) return fail(c, SQ_E_ARG, "the zero-coverage records must be kept indices in strictly ascending order");
+        sup.zidx.push_back(q[0]); sup.z_ochr.push_back(q[1]); sup.z_oright.push_back(q[2]);
+    }
+    if (S.nd == 0 || K == 0) return SQ_OK;
+    // the active stretches, as segment_prepare finds them (no shard; the whole stream is at hand: every shift is 0)
+    for (int k = 0; k < ncl; ++k) {
+        if (sup.trigger[k] >= K) break;
+        const int j = (int)(std::lower_bound(sup.zidx.begin(), sup.zidx.end(), sup.trigger[k]) - sup.zidx.begin());
+        if (P.active.empty() || P.active.back() != j) { P.active.push_back(j); P.first_cluster.push_back(k); }
+    }
+    P.shift.assign(P.active.size(), 0);
+    return SQ_OK;
+}
+
+int segment_plan_of_context(sq_ctx* c, std::shared_ptr<SegPlan>& plan) {
+    if (c->shard.on) return fail(c, SQ_E_ARG, "the debug entry of the segmentation automaton runs on an unsharded context");
+    int rc = dev_classify(c, nullptr);
+    if (rc) return rc;
+    std::vector<Blk> disc;
+    (void)segment_clusters(c, plan, disc);
+    int64_t trigger_last = 0, n_break = 0;
+    long long other_max = 0;
+    int32_t first_kept[2];
+    rc = segment_scan(c, *plan, false, trigger_last, other_max, first_kept);
+    if (rc) return rc;
+    return segment_prepare(c, *plan, n_break);
+}
+
+int segment_seeds_debug(sq_ctx* c, SegPlan& plan, int read_len, int route, const SegDevOut* emulated, SegSeedsDebug& out) {
+    out = SegSeedsDebug();
+    const int kept = c->read_len;
+    if (read_len > 0) c->read_len = read_len;
+    struct Back { sq_ctx* c; int v; ~Back() { c->read_len = v; } } back{c, kept};
+    std::vector<Node> seeds;
+    int rc = SQ_OK;
+    if (route == 0) {
+        std::string err;
+        long long ext3[3] = {0, 0, 0};
+        rc = replay_range(c, plan, 0, plan.active.size(), seeds, false, nullptr, err, nullptr, ext3);
+        if (rc) return fail(c, rc, err);
+        out.walk.stretches = (int64_t)plan.active.size();
+        for (int k = 0; k < 3; ++k) { out.walk.ext[k] = ext3[k]; out.walk.extended += ext3[k]; }
+    } else if (emulated) {
+        const SegDevTables* T = segment_device_tables(c, plan);
+        if (!T) { out.fallback = true; return SQ_OK; }
+        rc = segment_walk(c, plan, *T, *emulated, seeds, out.walk);
+    } else rc = segment_replay_device(c, plan, seeds, out.walk, out.fallback);
+    if (rc) return rc;
+    for (const Node& n : seeds) { out.seeds3.push_back(n.chr); out.seeds3.push_back(n.pos); out.seeds3.push_back(n.len); }
     return SQ_OK;
 }
 
