@@ -395,26 +395,26 @@ int bwa_seed_nodes_walk(sq_ctx* c, const HostBatch& hb, const int32_t rl5[5], co
     Carry last{1, 0, -1, -1, 0, 0};  // (what the stretch in front left behind: final)
     SeedRun again;
     for (int k = 0; k < np; ++k) {
-        const int32_t* R = D.report.data() + (size_t)BNR_ROW * (size_t)k;
+        const int32_t* R = D.report.data() + (size_t)bwn::REPORT * (size_t)k;
         const size_t lo = (size_t)D.cut[(size_t)k], hi = (size_t)D.cut[(size_t)k + 1];
         W.single += hi - lo == 1; W.longest = std::max<int64_t>(W.longest, (int64_t)(hi - lo));
         bool fine = true;
-        int other_right = R[BNR_OTHER_RIGHT];
+        int other_right = R[bwn::R_OTHER_RIGHT];
         if (k > 0) {
             fine = last.zero && last.dis_right == D.dis_in[(size_t)k] &&
-                   (last.other_right == 0 || R[BNR_MINPOS_OTH] == INT32_MAX || (long)last.other_right + RL_final < (long)R[BNR_MINPOS_OTH]);
-            if (fine && !(R[BNR_BITS] & 2)) other_right = last.other_right;  // (what the stretch did not assign stays the caller's)
+                   (last.other_right == 0 || R[bwn::R_MINPOS_OTH] == INT32_MAX || (long)last.other_right + RL_final < (long)R[bwn::R_MINPOS_OTH]);
+            if (fine && !(R[bwn::R_BITS] & bwn::B_OTH_SET)) other_right = last.other_right;  // (what the stretch did not assign stays the caller's)
         }
         if (fine) {
-            const int32_t* s3 = D.seeds3.data() + 3 * (size_t)R[BNR_SLICE];
-            for (int i = 0; i < R[BNR_SEEDS]; ++i) seeds.push_back(Node{s3[3 * i], s3[3 * i + 1], s3[3 * i + 2], 0, 0.0});
-            n_reads_records += R[BNR_READS];
-            W.flush_nodes += R[BNR_FLUSH_NODES]; W.marks_closed += R[BNR_MARKS_CLOSED];
-            read_len_out = R[BNR_RL];
-            last = Carry{(R[BNR_BITS] & 4) ? 1 : 0, R[BNR_PREV0], R[BNR_MARK_START], R[BNR_MARK_CHR], R[BNR_DIS_RIGHT], other_right};
+            const int32_t* s3 = D.seeds3.data() + 3 * (size_t)R[bwn::R_SPARE];
+            for (int i = 0; i < R[bwn::R_SEEDS]; ++i) seeds.push_back(Node{s3[3 * i], s3[3 * i + 1], s3[3 * i + 2], 0, 0.0});
+            n_reads_records += R[bwn::R_READS];
+            W.flush_nodes += R[bwn::R_FLUSH_NODES]; W.marks_closed += R[bwn::R_MARKS_CLOSED];
+            read_len_out = R[bwn::R_RL];
+            last = Carry{(R[bwn::R_BITS] & bwn::B_CLOSING_ZERO) ? 1 : 0, R[bwn::R_PREV0], R[bwn::R_MARK_START], R[bwn::R_MARK_CHR], R[bwn::R_DIS_RIGHT], other_right};
             continue;
         }
-        if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "device stretch %d (%d, %d) again: zero %d, rightmost values %d / %d against %d and first true tests at %d / %d\n", k, hb.refid[lo], hb.pos[lo], last.zero, last.dis_right, last.other_right, D.dis_in[(size_t)k], R[BNR_MINPOS_DIS], R[BNR_MINPOS_OTH]);
+        if (env_set("SQUID_BWA_DEBUG")) std::fprintf(stderr, "device stretch %d (%d, %d) again: zero %d, rightmost values %d / %d against %d and first true tests at %d / %d\n", k, hb.refid[lo], hb.pos[lo], last.zero, last.dis_right, last.other_right, D.dis_in[(size_t)k], R[bwn::R_MINPOS_DIS], R[bwn::R_MINPOS_OTH]);
         run_seed_stretch(again, hb, lo, hi, k + 1 < np, k == 0, c->read_len, RL_final, D.dis_in[(size_t)k], &last, false);
         ++W.again;
         seeds.insert(seeds.end(), again.seeds.begin(), again.seeds.end());

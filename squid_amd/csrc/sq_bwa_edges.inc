@@ -15,24 +15,7 @@
 #include "sq_wave.h"
 #include "sq_chim_stage.inc"
 namespace bwe {
-constexpr uint8_t AUX_MULTI = 1, AUX_LOWPHRED = 4;  // SQ_AUX_MULTI, SQ_AUX_LOWPHRED
-// the byte count_record leaves per record: kind (0 = skipped or locates nothing, 1 = first mate, 2 = multi-aligned second mate), `part`,
-// the mate stub, and how the own blocks stand in read-offset order (0 = as stored, 1 = reversed, 2 = neither: ranked in fill_record)
-enum : uint8_t { M_KIND = 3, M_PART = 4, M_STUB = 8, M_ORDER_SHIFT = 4 };
-// the byte edge_fragment leaves per record: which of the three lists it joins
-enum : uint8_t { B_PART = 1, B_FIRST_DIS = 2, B_SECOND = 4 };
-// next to chs::FLAG_FULL / chs::FLAG_ASSERT: two own blocks of one record share a read offset (std::sort's order is then not defined)
-enum : uint32_t { FLAG_TIE = 16 };
-
-struct Recs {
-    int64_t n;
-    const int32_t *refid, *pos, *mrefid, *mpos;
-    const uint16_t *flag, *totlen;
-    const uint8_t *mapq, *aux;
-    const uint32_t* blk_off;
-    const int32_t *b_refpos, *b_matchref;
-    const uint16_t *b_readpos, *b_matchread;
-};
+using sq::RecCols;
 // chs::Frags while it is being written
 struct FragsW {
     uint32_t *off, *na;
@@ -44,12 +27,12 @@ struct FragsW {
 };
 
 // prepare() up to the kind and `part`; cnt[r] = blocks of the record's entry
-WV_FN void count_record(const Recs& R, uint8_t* meta, int32_t* cnt, uint32_t* flags, int64_t r) {
+WV_FN void count_record(const RecCols& R, uint8_t* meta, int32_t* cnt, uint32_t* flags, int64_t r) {
     if (r >= R.n) return;
     meta[r] = 0; cnt[r] = 0;
     const int flag = R.flag[r];
     if ((flag & 0x400) || (flag & 0x4)) return;
-    const bool first = (flag & 0x40) != 0, multi = (R.aux[r] & AUX_MULTI) != 0, low = (R.aux[r] & AUX_LOWPHRED) != 0;
+    const bool first = (flag & 0x40) != 0, multi = (R.aux[r] & SQ_AUX_MULTI) != 0, low = (R.aux[r] & SQ_AUX_LOWPHRED) != 0;
     if (first ? (multi || R.mapq[r] == 0) : !multi) return;  // :1723-1726 (W5)
     const uint32_t b0 = R.blk_off[r], nown = R.blk_off[r + 1] - b0;
     if (nown == 0) return;
@@ -77,7 +60,7 @@ WV_FN void count_record(const Recs& R, uint8_t* meta, int32_t* cnt, uint32_t* fl
     cnt[r] = kind == 0 ? 0 : (kind == 1 ? (int32_t)nown : 1) + (stub ? 1 : 0);
 }
 // the own block that stands at place k of the read-offset order (ties, flagged by count_record, by index)
-WV_FN uint32_t own_at(const Recs& R, uint32_t b0, uint32_t nown, uint8_t order, uint32_t k) {
+WV_FN uint32_t own_at(const RecCols& R, uint32_t b0, uint32_t nown, uint8_t order, uint32_t k) {
     if (order == 0) return k;
     if (order == 1) return nown - 1 - k;
     for (uint32_t j = 0; j < nown; ++j) {
@@ -89,12 +72,12 @@ WV_FN uint32_t own_at(const Recs& R, uint32_t b0, uint32_t nown, uint8_t order, 
     return 0;
 }
 // the entry of record r behind the scan of the counts (off[r] is there; off[n] is the scan's total): what finish_prepare leaves
-WV_FN void fill_record(const Recs& R, const uint8_t* meta, const FragsW& F, int64_t r) {
+WV_FN void fill_record(const RecCols& R, const uint8_t* meta, const FragsW& F, int64_t r) {
     if (r >= R.n) return;
     const uint8_t m = meta[r], kind = m & M_KIND, order = m >> M_ORDER_SHIFT;
     const bool stub = (m & M_STUB) != 0;
     const int flag = R.flag[r];
-    const bool first = (flag & 0x40) != 0, low = (R.aux[r] & AUX_LOWPHRED) != 0;
+    const bool first = (flag & 0x40) != 0, low = (R.aux[r] & SQ_AUX_LOWPHRED) != 0;
     F.na[r] = kind == 1 ? R.blk_off[r + 1] - R.blk_off[r] : (kind == 2 && stub ? 1u : 0u);
     F.atot[r] = first ? (int32_t)R.totlen[r] : 0; F.btot[r] = first ? 0 : (int32_t)R.totlen[r];
     F.low[r] = (uint8_t)(low ? (first ? 1 : 2) : 0);

@@ -26,37 +26,18 @@
 // host route.
 #pragma once
 #include "sq_wave.h"
+#include "sq_stage_layout.h"
 namespace bwn {
-constexpr uint8_t AUX_MULTI = 1, AUX_LOWPHRED = 4;  // SQ_AUX_MULTI, SQ_AUX_LOWPHRED
-// the class byte: PASS1 = behind the filter of :871 (seed_step's first return), PASS = it also has a block (seed_record_passes), DISC = not
-// pair_concordant, CLIP = concordant and clipped (the partial window), REV, RP15 = first block at a read offset above 15, CUT = gap record
-enum : uint8_t { N_PASS1 = 1, N_PASS = 2, N_DISC = 4, N_CLIP = 8, N_REV = 16, N_RP15 = 32, N_CUT = 64 };
-constexpr uint8_t W_MASK = N_PASS | N_DISC | N_CLIP, W_CONC = N_PASS, W_PART = N_PASS | N_CLIP, W_DIS = N_PASS | N_DISC;
-enum : uint32_t { FLAG_UNSORTED = 1, FLAG_SEEDS_FULL = 2, FLAG_MARGINS_FULL = 4, FLAG_GUARD = 8 };
-constexpr int TILE_ROUNDS = 16, TILE_RECS = 64 * TILE_ROUNDS;  // records of one wave of the tile kernels
-// one row per stretch
-enum { R_RL = 0, R_PREV0, R_MARK_START, R_MARK_CHR, R_DIS_RIGHT, R_OTHER_RIGHT, R_BITS, R_MINPOS_DIS, R_MINPOS_OTH, R_READS, R_SEEDS, R_FLUSH_NODES, R_FLUSHES, R_COVER_FAILS, R_MARKS_CLOSED, R_SPARE, REPORT };
-enum { B_DIS_SET = 1, B_OTH_SET = 2, B_CLOSING_ZERO = 4 };
-constexpr int THRESH = 3;
-
-struct Recs {
-    int64_t n;
-    const int32_t *refid, *pos, *mrefid, *mpos;
-    const uint16_t *flag, *totlen;
-    const uint8_t *mapq, *aux;
-    const uint32_t* blk_off;
-    const int32_t *b_refpos, *b_matchref;
-    const uint16_t *b_readpos, *b_matchread;
-};
+using sq::RecCols;
 WV_FN int imax(int a, int b) { return a > b ? a : b; }
 WV_FN int imin(int a, int b) { return a < b ? a : b; }
 
 // ---- lane-local: the class byte and the first block of record r
-WV_FN void class_record(const Recs& R, uint8_t* cls, int32_t* p0, int32_t* e0, int64_t r) {
+WV_FN void class_record(const RecCols& R, uint8_t* cls, int32_t* p0, int32_t* e0, int64_t r) {
     if (r >= R.n) return;
     cls[r] = 0; p0[r] = 0; e0[r] = 0;
     const int flag = R.flag[r], rid = R.refid[r];
-    if ((R.aux[r] & AUX_MULTI) || R.mapq[r] == 0 || (flag & 0x400) || (flag & 0x4) || rid == -1) return;
+    if ((R.aux[r] & SQ_AUX_MULTI) || R.mapq[r] == 0 || (flag & 0x400) || (flag & 0x4) || rid == -1) return;
     uint8_t cl = N_PASS1;
     const uint32_t b0 = R.blk_off[r], nb = R.blk_off[r + 1] - b0;
     if (nb != 0) {
@@ -71,7 +52,7 @@ WV_FN void class_record(const Recs& R, uint8_t* cls, int32_t* p0, int32_t* e0, i
         }
         const int rp0 = R.b_readpos[b0], bl = (int)(b0 + nb - 1);
         if (!conc) cl |= N_DISC;
-        else if (!(R.aux[r] & AUX_LOWPHRED) && (rp0 > 15 || (int)R.totlen[r] - (int)R.b_readpos[bl] - (int)R.b_matchread[bl] > 15)) cl |= N_CLIP;
+        else if (!(R.aux[r] & SQ_AUX_LOWPHRED) && (rp0 > 15 || (int)R.totlen[r] - (int)R.b_readpos[bl] - (int)R.b_matchread[bl] > 15)) cl |= N_CLIP;
         if (rev) cl |= N_REV;
         if (rp0 > 15) cl |= N_RP15;
         p0[r] = R.b_refpos[b0]; e0[r] = R.b_refpos[b0] + R.b_matchref[b0];

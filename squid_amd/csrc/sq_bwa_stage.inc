@@ -17,42 +17,30 @@
 // wave max-scan, the test, runs of equal m reduced inside the wave, one atomic add per (wave, node) for the count and one for the sum).
 #pragma once
 #include "sq_wave.h"
+#include "sq_stage_layout.h"
 namespace bws {
-// bits of the class byte (CLS_P3 is the C_P3 of the record kernels: dev_breakpoint_support reads it; CLS_READS is free there)
-enum : uint8_t { CLS_P3 = 4, CLS_READS = 64 };
-constexpr uint8_t AUX_MULTI = 1;  // SQ_AUX_MULTI
-constexpr int FINE_SHIFT = 10;    // NODE_FINE_SHIFT
-constexpr int TILE_ROUNDS = 16, TILE_BLOCKS = 64 * TILE_ROUNDS;  // blocks of one wave
-enum : uint32_t { CNT_HELD = 0, CNT_DECREASING = 1 };
-
-struct Recs {
-    int64_t n;
-    const int32_t *refid, *pos, *mrefid, *mpos;
-    const uint16_t* flag;
-    const uint8_t *mapq, *aux;
-    const uint32_t* blk_off;
-};
-// READS: the record feeds Reads (:871-881, seed_record_passes).  P3: ExactBPConcordantSupport looks at it (:3136-3142, decide() of
+using sq::RecCols;
+// C_READS: the record feeds Reads (:871-881, seed_record_passes).  C_P3: ExactBPConcordantSupport looks at it (:3136-3142, decide() of
 // bwa_breakpoint_support); in_names (may be null: no name is in the set): one byte per record, the raw QNAME is a rebuilt fragment's
-WV_FN uint8_t class_of(const Recs& R, int min_mapqual, const uint8_t* in_names, int64_t r) {
+WV_FN uint8_t class_of(const RecCols& R, int min_mapqual, const uint8_t* in_names, int64_t r) {
     const int flag = R.flag[r], rid = R.refid[r], mapq = R.mapq[r];
-    if ((R.aux[r] & AUX_MULTI) || (flag & 0x400) || (flag & 0x4) || rid == -1) return 0;
+    if ((R.aux[r] & SQ_AUX_MULTI) || (flag & 0x400) || (flag & 0x4) || rid == -1) return 0;
     uint8_t cl = 0;
-    if (mapq != 0 && R.blk_off[r + 1] != R.blk_off[r]) cl |= CLS_READS;
+    if (mapq != 0 && R.blk_off[r + 1] != R.blk_off[r]) cl |= sq::C_READS;
     if (mapq >= min_mapqual) {
         const int mp = R.mpos[r], p = R.pos[r];
         const bool same_chr_mate = !(flag & 0x8) && R.mrefid[r] == rid;
         const bool left = same_chr_mate && (mp > p || (mp == p && (flag & 0x80)));  // (at equal positions the second mate is the one dropped)
-        if (!left && !(in_names && in_names[r])) cl |= CLS_P3;
+        if (!left && !(in_names && in_names[r])) cl |= sq::C_P3;
     }
     return cl;
 }
 // one lane per record: the class byte, and per block of the record the chromosome (-1: the record does not feed Reads)
-WV_FN void classify(const Recs& R, int min_mapqual, const uint8_t* in_names, uint8_t* cls, int32_t* blk_chr, int64_t r) {
+WV_FN void classify(const RecCols& R, int min_mapqual, const uint8_t* in_names, uint8_t* cls, int32_t* blk_chr, int64_t r) {
     const uint8_t cl = class_of(R, min_mapqual, in_names, r);
     cls[r] = cl;
     if (!blk_chr) return;
-    const int32_t c = (cl & CLS_READS) ? R.refid[r] : -1;
+    const int32_t c = (cl & sq::C_READS) ? R.refid[r] : -1;
     for (uint32_t b = R.blk_off[r], e = R.blk_off[r + 1]; b < e; ++b) blk_chr[b] = c;
 }
 
@@ -69,7 +57,7 @@ WV_FN int first_node_behind(const Nodes& N, int c, int p) {
     int lo, hi;
     if (N.fine) {
         const int first = N.fine_off[c], last = N.fine_off[c + 1] - 2;
-        int b = first + (p < 0 ? 0 : (p >> FINE_SHIFT));
+        int b = first + (p < 0 ? 0 : (p >> sq::NODE_FINE_SHIFT));
         if (b > last) b = last;
         lo = N.fine[b]; hi = N.fine[b + 1];
     } else {

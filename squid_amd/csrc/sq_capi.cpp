@@ -1683,20 +1683,10 @@ int sq_debug_bwa_raw_edges_tables(sq_ctx* c, int32_t route, int32_t n_nodes, con
             N[(size_t)i] = Node{nodes3[3 * i], nodes3[3 * i + 1], nodes3[3 * i + 2], 0, 0.0};
             if (N[(size_t)i].chr < 0 || (i && N[(size_t)i].chr < N[(size_t)i - 1].chr)) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: node chromosomes must be non-negative and sorted");
         }
-        if (blk_off[0] != 0) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: blk_off must start at 0");
-        for (int64_t r = 0; r < n_rec; ++r) if (blk_off[r + 1] < blk_off[r]) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: blk_off must not go down");
-        const size_t nb = blk_off[n_rec];
-        if (nb && !blk4) return SQ_E_ARG;
-        if (n_nodes == 0 && n_rec != 0) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: records need a node table");
         HostBatch hb;
-        for (int64_t r = 0; r < n_rec; ++r) {
-            const int32_t* q = rec8 + 8 * r;
-            hb.refid.push_back(q[0]); hb.pos.push_back(q[1]); hb.mrefid.push_back(q[2]); hb.mpos.push_back(q[3]); hb.endpos.push_back(q[1]);
-            hb.flag.push_back((uint16_t)q[4]); hb.totlen.push_back((uint16_t)q[5]); hb.mapq.push_back((uint8_t)q[6]); hb.aux.push_back((uint8_t)q[7]);
-        }
-        hb.blk_off.assign(blk_off, blk_off + n_rec + 1);
-        hb.name_off.assign((size_t)n_rec + 1, 0);
-        for (size_t b = 0; b < nb; ++b) { hb.b_refpos.push_back(blk4[4 * b]); hb.b_matchref.push_back(blk4[4 * b + 1]); hb.b_readpos.push_back((uint16_t)blk4[4 * b + 2]); hb.b_matchread.push_back((uint16_t)blk4[4 * b + 3]); }
+        const int rc = batch_from_tables(c, "sq_debug_bwa_raw_edges_tables", n_rec, rec8, blk_off, blk4, hb);
+        if (rc) return rc;
+        if (n_nodes == 0 && n_rec != 0) return fail(c, SQ_E_ARG, "sq_debug_bwa_raw_edges_tables: records need a node table");
         return bwa_edges_debug_view(c, &hb, N, route, out);
     });
 }

@@ -15,6 +15,7 @@
 // position behind soft fragment k.  hint_of() then gives every fragment its exact incoming position.
 #pragma once
 #include "sq_wave.h"
+#include "sq_stage_layout.h"
 namespace chs {
 struct Nodes { int32_t n; const int32_t *chr, *pos, *len; };
 // fragment table (SoA, never written by a kernel): blocks of fragment q = [off[q], off[q + 1]), mate a first (na[q] blocks), then mate b
@@ -32,8 +33,6 @@ struct Blk { int32_t refid, refpos, readpos, matchref, matchread; bool rev; };
 struct Params { int32_t dp, di; };
 // position chain of one stage
 struct Chain { int32_t *pin, *lastdeep, *spos; uint32_t* soft; int32_t* sout; uint8_t* cls; uint32_t soft_cap; };
-enum : uint8_t { CLS_NONE = 0, CLS_DEEP = 1, CLS_SOFT = 2 };
-enum : uint32_t { FLAG_FULL = 4, FLAG_ASSERT = 8 };
 
 WV_FN int imin(int a, int b) { return a < b ? a : b; }
 WV_FN int imax(int a, int b) { return a > b ? a : b; }

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/squid_hip.h"
+#include "sq_stage_layout.h"
 
 namespace sq {
 
@@ -143,17 +144,6 @@ struct GraphSnap {  // flattened copy for sq_graph_view
     void take(const std::vector<Node>& N, const std::vector<Edge>& E, const std::vector<int32_t>* lab);
     void view(sq_graph* g) const;
 };
-
-// per-record summary of the kept pass-1 stream, produced on the GPU for the host segmentation automaton
-struct StreamRec {
-    int32_t refid, pos;      // record.RefID / record.Position
-    int32_t fb_refpos, fb_matchref;  // first aligned block in CIGAR order (ReadsMain / window element)
-    uint16_t fb_readpos;
-    uint8_t flags;           // SR_* bits
-    uint8_t nrest;           // number of further blocks (saturated at 255)
-    uint32_t rest_off;       // offset of the further blocks in the rest arrays
-};
-enum : uint8_t { SR_HASBLK = 1, SR_CONC = 2, SR_PART = 4, SR_REV = 8, SR_MATE = 16 /* 0x40 or 0x80 set */ };
 
 struct Timer {
     std::vector<const char*> names;
@@ -409,6 +399,10 @@ struct HostBatch {  // owning storage behind an sq_aln_batch
     void append_parts(const std::vector<HostBatch>& parts, int count);  // the same for parts[0 .. count), copied side by side
     void view(sq_aln_batch* b, bool with_names) const;
     size_t size() const { return refid.size(); }
+    RecCols cols() const {
+        return RecCols{(int64_t)size(), refid.data(), pos.data(), mrefid.data(), mpos.data(), flag.data(), totlen.data(), mapq.data(), aux.data(), blk_off.data(),
+                       b_refpos.data(), b_matchref.data(), b_readpos.data(), b_matchread.data()};
+    }
 };
 void drop_file_cache();
 void drop_whole_file_scratch();  // host scratch of whole-file reads (sq_release_reader_buffers)
@@ -463,11 +457,8 @@ struct SegDevTables {
     int64_t n_recs = 0, node_slots = 0, longest = 0;
     const StreamRec* recs = nullptr;  // the host copy of the summaries (the device keeps its own: DeviceRecords::srec)
 };
-// report: na rows of sgs::REPORT values; nodes3: node_slots nodes (chr, pos, len), a stretch's slice starts at its S_NODE_OFF
+// report: na rows of sgs::REPORT values (sq_stage_layout.h); nodes3: node_slots nodes (chr, pos, len), a stretch's slice starts at its S_NODE_OFF
 struct SegDevOut { std::vector<int32_t> report, nodes3; };
-enum { SGR_FLAGS = 0, SGR_NODES, SGR_MINCHR, SGR_BOUND, SGR_NSENS, SGR_SENS, SGR_EXT = SGR_SENS + 4, SGR_CLUSTERS = SGR_EXT + 3, SGR_SUBS, SGR_MMAX, SGR_SPARE, SGR_ROW };  // (sgs::R_*)
-enum { SGF_CONSULTED = 1, SGF_EXIST = 2, SGF_M_FULL = 4, SGF_CAPACITY = 4 | 8 | 16 | 32 };                                                                             // (sgs::F_*)
-enum { SGT_LO = 0, SGT_HI, SGT_KC, SGT_SHIFT, SGT_OCHR, SGT_ORIGHT, SGT_NODE_OFF, SGT_NODE_CAP, SGT_ROW };                                                             // (sgs::S_*)
 struct SegWalk { int64_t stretches = 0, again = 0, longest = 0, kept_with_nodes = 0, sens = 0, extended = 0, ext[3] = {0, 0, 0}, flagged = 0, flagged_margins = 0, sens_hits = 0, leading_kept = 0; };
 // null: the plan is too large for the route's tables (the caller takes segment_replay)
 const SegDevTables* segment_device_tables(const sq_ctx* c, SegPlan& plan);
@@ -601,7 +592,7 @@ int dev_exact_breakpoints_start(sq_ctx* c, bool& fallback);  // queued behind th
 int dev_exact_breakpoints_collect(sq_ctx* c, BPMap& bp);
 void dev_chim_drop_pending(sq_ctx* c);
 // --bwa on the device (sq_bwa_stage.inc): the host batch into the record table; the class byte of every record (in_names: one host byte per
-// record or null, see bws::class_of) with the counts of READS records, C_P3 records and Reads blocks; the node depth kernels over the
+// record or null, see bws::class_of) with the counts of C_READS records, C_P3 records and Reads blocks; the node depth kernels over the
 // table behind dev_upload_nodes (fallback: a chromosome goes down along Reads, nothing is returned); the same kernels on flat tables
 int dev_bwa_upload(sq_ctx* c, const HostBatch& hb);
 int dev_bwa_classify(sq_ctx* c, const uint8_t* in_names, int64_t& n_reads, int64_t& n_p3, int64_t& n_reads_blocks);
@@ -621,9 +612,7 @@ struct BwaEdgesOut {
 int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& out);
 // --bwa: the record automaton of BuildNode_BWA over the resident table (sq_bwa_nodes.inc).  read_len: the value the loop starts with, rl5: behind
 // each of the first five records.  cut: np + 1 stretch boundaries; dis_in: the dis_right every stretch was started with; report: np rows of
-// bwn::REPORT values (R_SPARE: where the stretch's seeds start in seeds3, in seeds); fallback: see dev_bwa_seed_nodes
-enum { BNR_RL = 0, BNR_PREV0, BNR_MARK_START, BNR_MARK_CHR, BNR_DIS_RIGHT, BNR_OTHER_RIGHT, BNR_BITS, BNR_MINPOS_DIS, BNR_MINPOS_OTH, BNR_READS, BNR_SEEDS, BNR_FLUSH_NODES, BNR_FLUSHES, BNR_COVER_FAILS,
-       BNR_MARKS_CLOSED, BNR_SLICE, BNR_ROW };  // (bwn::R_*; BNR_BITS: 1 dis_set, 2 oth_set, 4 closing_zero)
+// bwn::REPORT values (sq_stage_layout.h); fallback: see dev_bwa_seed_nodes
 struct BwaNodesOut {
     std::vector<int32_t> cut, dis_in, report, seeds3;
     bool fallback = false;

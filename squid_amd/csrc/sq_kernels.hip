@@ -61,6 +61,7 @@ struct RecView {  // raw device pointers, passed by value to kernels
     // the fixed part of a record (32 bytes) as TWO 16-byte words side by side, read only by k_pass1, which wants every
     // field: {refid, pos, mate refid, mate pos} {flag | totlen << 16, mapq | aux << 8 | own blocks << 16, blk_off, end} (k_pack_records)
     const int4* r_pack;
+    RecCols cols() const { return RecCols{n, refid, pos, mrefid, mpos, flag, totlen, mapq, aux, blk_off, b_refpos, b_matchref, b_readpos, b_matchread}; }
 };
 struct NodeView {
     int32_t n, n_ref;
@@ -74,7 +75,6 @@ struct NodeView {
     const int32_t* bucket_off;  // geometry of the 16 KiB index the breakpoint table uses (BPView)
     const int4* pack;  // chr, pos, len, 0 of a node as one 16-byte load (k_node_pack)
 };
-constexpr int NODE_BUCKET_SHIFT = 14, NODE_FINE_SHIFT = 10;
 
 template <typename T>
 struct DBuf {
@@ -90,6 +90,8 @@ struct DBuf {
         if (e == hipSuccess) cap = want;
         return e;
     }
+    // for a route with a way back to the host: false = the buffer could not be had; the HIP error is cleared and the caller goes back
+    bool try_reserve(size_t n) { if (reserve(n) == hipSuccess) return true; (void)hipGetLastError(); return false; }
     hipError_t grow_keep(size_t used, size_t n, hipStream_t s) {  // keep the first `used` elements
         if (n <= cap) return hipSuccess;
         size_t want = std::max(n + n / 2, (size_t)1 << 16);
@@ -346,10 +348,7 @@ struct DeviceRecords {
     }
 };
 
-// classification bits (cls)
-enum : uint8_t { C_P2 = 1, C_P1 = 2, C_P3 = 4, C_CONC = 8, C_PART = 16, C_HASSTUB = 32 };
-static_assert(bws::CLS_P3 == C_P3 && (bws::CLS_READS & (C_P2 | C_P1 | C_P3 | C_CONC | C_PART | C_HASSTUB)) == 0, "the --bwa class byte shares C_P3 with the record kernels");
-static_assert(bws::AUX_MULTI == SQ_AUX_MULTI && bws::FINE_SHIFT == NODE_FINE_SHIFT, "sq_bwa_stage.inc restates these");
+// (the classification bits of cls, C_*: sq_stage_layout.h)
 // keep bits
 enum : uint8_t { K_1 = 1, K_2 = 2, K_BUILD = 4, K_P3 = 8 /* copy of the class bit C_P3: the edge stage makes the breakpoint-cursor keys without reading the class byte */ };
 
@@ -5239,16 +5238,16 @@ void dev_chim_drop_pending(sq_ctx* c) {
 }
 
 // ------------------------------------------------------------------------------------------------ --bwa on the device (sq_bwa_stage.inc)
-__global__ __launch_bounds__(256) void k_bwa_classify(bws::Recs R, int min_mapqual, const uint8_t* in_names, uint8_t* cls, int32_t* blk_chr, uint32_t* counts /* READS records, C_P3 records, Reads blocks */) {
+__global__ __launch_bounds__(256) void k_bwa_classify(RecCols R, int min_mapqual, const uint8_t* in_names, uint8_t* cls, int32_t* blk_chr, uint32_t* counts /* READS records, C_P3 records, Reads blocks */) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint8_t cl = 0;
     uint32_t nblk = 0;
     if (r < R.n) {
         bws::classify(R, min_mapqual, in_names, cls, blk_chr, r);
         cl = cls[r];
-        if (cl & bws::CLS_READS) nblk = R.blk_off[r + 1] - R.blk_off[r];
+        if (cl & C_READS) nblk = R.blk_off[r + 1] - R.blk_off[r];
     }
-    const uint32_t n_reads = (uint32_t)__popcll(__ballot(cl & bws::CLS_READS)), n_p3 = (uint32_t)__popcll(__ballot(cl & bws::CLS_P3));
+    const uint32_t n_reads = (uint32_t)__popcll(__ballot(cl & C_READS)), n_p3 = (uint32_t)__popcll(__ballot(cl & C_P3));
     const uint32_t blocks = wv::scan_incl_add(nblk);
     if ((threadIdx.x & 63) == 63) {
         if (n_reads) atomicAdd(counts, n_reads);
@@ -5298,8 +5297,7 @@ int dev_bwa_classify(sq_ctx* c, const uint8_t* in_names, int64_t& n_reads, int64
     }
     uint32_t* counts = (uint32_t*)D.flags.p + 40;
     HIPCHK(hipMemsetAsync(counts, 0, 3 * sizeof(uint32_t), s));
-    const RecView V = D.view();
-    const bws::Recs R{n, V.refid, V.pos, V.mrefid, V.mpos, V.flag, V.mapq, V.aux, V.blk_off};
+    const RecCols R = D.view().cols();
     { EvTimer t(c, "k_bwa_classify", 22.0 * n + (in_names ? 0.0 : 4.0 * D.nb));
       // (the chromosome per block is written with the READS bit; the second launch of a graph only adds C_P3)
       hipLaunchKernelGGL(k_bwa_classify, grid_for(n, 256), dim3(256), 0, s, R, (int)c->P.min_mapqual, in_names ? D.bwa_names.p : (const uint8_t*)nullptr, D.cls.p, in_names ? (int32_t*)nullptr : D.bwa_blk_chr.p, counts); }
@@ -5375,8 +5373,8 @@ int dev_bwa_node_depth_flat(sq_ctx* c, int32_t n_nodes, const int32_t* nodes3, i
 
 // ------------------------------------------------------------------------------------------------ --bwa: RawEdges' record loop on the device
 // (sq_bwa_edges_on_device; the kernels' bodies are in sq_bwa_edges.inc, the position chain is chim_chain over the table made here)
-__global__ __launch_bounds__(256) void k_bwa_frag_count(bwe::Recs R, uint8_t* meta, int32_t* cnt, uint32_t* flags) { bwe::count_record(R, meta, cnt, flags, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
-__global__ __launch_bounds__(256) void k_bwa_frag_fill(bwe::Recs R, const uint8_t* meta, bwe::FragsW F) { bwe::fill_record(R, meta, F, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_bwa_frag_count(RecCols R, uint8_t* meta, int32_t* cnt, uint32_t* flags) { bwe::count_record(R, meta, cnt, flags, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_bwa_frag_fill(RecCols R, const uint8_t* meta, bwe::FragsW F) { bwe::fill_record(R, meta, F, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ __launch_bounds__(256) void k_bwa_edge_fragment(chs::Nodes N, chs::Frags F, chs::Trim T, int32_t* rn, chs::Chain C, chs::Params P, const uint8_t* meta, unsigned long long* hk, uint32_t* hv,
                                                            uint32_t mask, uint32_t* flags, uint8_t* bits, int32_t* final_pos) {
     bwe::edge_fragment(N, F, T, rn, C, P, meta, hk, hv, mask, flags, bits, final_pos, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
@@ -5386,8 +5384,6 @@ __global__ __launch_bounds__(256) void k_bwa_edge_lists(chs::Frags F, const int3
     bwe::scatter_lists(F, rn, bits, at_part, at_first, at_second, l_part, l_first, l_second, second_keys, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 struct FBwaBit { const uint8_t* bits; uint8_t bit; __device__ int operator()(int64_t i) const { return (bits[i] & bit) ? 1 : 0; } };
-static_assert(bwe::AUX_MULTI == SQ_AUX_MULTI && bwe::AUX_LOWPHRED == SQ_AUX_LOWPHRED, "sq_bwa_edges.inc restates these");
-static_assert((bwe::FLAG_TIE & (chs::FLAG_FULL | chs::FLAG_ASSERT)) == 0, "one flag word");
 
 // The BAM loop of RawEdges over the resident table of a --bwa batch, on the node table `nodes`.  out.fallback (with out.why): nothing of
 // `out` is valid and the caller takes the host loop -- the table is not resident, two own blocks of a record share a read offset, a
@@ -5406,12 +5402,12 @@ int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& ou
     if ((unsigned long long)D.nb + (unsigned long long)nf >= 0x7fffffffull) return back("more than 2^31 block slots");
     S.version = 0;  // (whatever fragment table the chimeric stages had is gone)
     S.stage.reset();
-#define BWE_RESERVE(buf, count) do { if ((buf).reserve((size_t)(count)) != hipSuccess) { (void)hipGetLastError(); return back("a device buffer could not be had (SQ_E_CAPACITY)"); } } while (0)
-    BWE_RESERVE(S.e_rec, 4 * (size_t)nf + 8); BWE_RESERVE(S.e_low, nf); BWE_RESERVE(S.e_meta, nf); BWE_RESERVE(S.e_bits, nf);
-    BWE_RESERVE(S.pin, nf); BWE_RESERVE(S.lastdeep, nf); BWE_RESERVE(S.spos, nf); BWE_RESERVE(S.cls, nf); BWE_RESERVE(S.soft, nf + 1); BWE_RESERVE(S.sout, nf + 1); BWE_RESERVE(S.flags, 16);
+    const char* const no_buffer = "a device buffer could not be had (SQ_E_CAPACITY)";
+    if (!(S.e_rec.try_reserve(4 * (size_t)nf + 8) && S.e_low.try_reserve(nf) && S.e_meta.try_reserve(nf) && S.e_bits.try_reserve(nf) && S.pin.try_reserve(nf) && S.lastdeep.try_reserve(nf) &&
+          S.spos.try_reserve(nf) && S.cls.try_reserve(nf) && S.soft.try_reserve(nf + 1) && S.sout.try_reserve(nf + 1) && S.flags.try_reserve(16)))
+        return back(no_buffer);
     HIPCHK(hipMemsetAsync(S.flags.p, 0, 16 * 4, s));
-    const RecView V = D.view();
-    const bwe::Recs R{nf, V.refid, V.pos, V.mrefid, V.mpos, V.flag, V.totlen, V.mapq, V.aux, V.blk_off, V.b_refpos, V.b_matchref, V.b_readpos, V.b_matchread};
+    const RecCols R = D.view().cols();
     bwe::FragsW W{};
     W.off = S.e_rec.p; W.na = W.off + nf + 1; W.atot = (int32_t*)(W.na + nf); W.btot = W.atot + nf; W.low = S.e_low.p;
     uint32_t* h = S.stage.take_n<uint32_t>(16);
@@ -5425,7 +5421,7 @@ int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& ou
     if (h[1] & bwe::FLAG_TIE) return back("two blocks of one record share a read offset");
     const int64_t nblk = (int64_t)h[0], nb1 = std::max<int64_t>(nblk, 1);
     if (nblk < 0 || nblk > D.nb + nf) return fail(c, SQ_E_ARG, "internal: the fragment table of the --bwa edge stage is larger than its records allow");
-    BWE_RESERVE(S.e_blk, 5 * nb1); BWE_RESERVE(S.e_rev, nb1); BWE_RESERVE(S.trim, 4 * nb1); BWE_RESERVE(S.rn, nb1);
+    if (!(S.e_blk.try_reserve(5 * nb1) && S.e_rev.try_reserve(nb1) && S.trim.try_reserve(4 * nb1) && S.rn.try_reserve(nb1))) return back(no_buffer);
     W.refid = S.e_blk.p; W.refpos = W.refid + nb1; W.readpos = W.refpos + nb1; W.matchref = W.readpos + nb1; W.matchread = W.matchref + nb1; W.rev = S.e_rev.p;
     { EvTimer t(c, "k_bwa_frag_fill", 30.0 * nf + 33.0 * nblk); hipLaunchKernelGGL(k_bwa_frag_fill, grid_for(nf, 256), dim3(256), 0, s, R, S.e_meta.p, W); }
     S.nf = nf; S.nblk = nblk;
@@ -5442,7 +5438,7 @@ int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& ou
     while (S.h_slots < (1u << 28) && (size_t)S.h_slots < 4 * nodes.size()) S.h_slots <<= 1;
     for (bool first = true;; first = false) {  // the table starts small and grows when it fills up (unique edges are few)
         const uint32_t slots = S.h_slots;
-        BWE_RESERVE(S.hkey, slots); BWE_RESERVE(S.hval, slots); BWE_RESERVE(S.okey, slots); BWE_RESERVE(S.oval, slots);
+        if (!(S.hkey.try_reserve(slots) && S.hval.try_reserve(slots) && S.okey.try_reserve(slots) && S.oval.try_reserve(slots))) return back(no_buffer);
         HIPCHK(hipMemsetAsync(S.hkey.p, 0xff, (size_t)slots * 8, s));
         HIPCHK(hipMemsetAsync(S.hval.p, 0, (size_t)slots * 4, s));
         if (!first) HIPCHK(hipMemsetAsync(S.flags.p, 0, 4 * 4, s));  // (flags[4], the soft count, stays)
@@ -5470,8 +5466,7 @@ int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& ou
     HIPCHK(hipStreamSynchronize(s));
     const size_t n_part = h[8], n_first = h[9], n_second = h[10];
     if (n_part > (size_t)nf || n_first > (size_t)nf || n_second > (size_t)nf) return fail(c, SQ_E_ARG, "internal: a list of the --bwa edge stage is longer than the table");
-    BWE_RESERVE(S.e_lists, n_part + n_first + n_second + 1); BWE_RESERVE(S.e_skeys, n_second + 1);
-#undef BWE_RESERVE
+    if (!(S.e_lists.try_reserve(n_part + n_first + n_second + 1) && S.e_skeys.try_reserve(n_second + 1))) return back(no_buffer);
     uint32_t *l_part = S.e_lists.p, *l_first = l_part + n_part, *l_second = l_first + n_first;
     { EvTimer t(c, "k_bwa_edge_lists", 13.0 * nf);
       hipLaunchKernelGGL(k_bwa_edge_lists, grid_for(nf, 256), dim3(256), 0, s, F, S.rn.p, S.e_bits.p, S.pin.p, S.lastdeep.p, S.spos.p, l_part, l_first, l_second, S.e_skeys.p); }
@@ -5486,7 +5481,7 @@ int dev_bwa_raw_edges(sq_ctx* c, const std::vector<Node>& nodes, BwaEdgesOut& ou
 
 // ------------------------------------------------------------------------------------------------ --bwa: BuildNode_BWA's record automaton on the device
 // (sq_bwa_nodes_on_device; the kernels' bodies are in sq_bwa_nodes.inc)
-__global__ __launch_bounds__(256) void k_bwa_node_class(bwn::Recs R, uint8_t* cls, int32_t* p0, int32_t* e0) { bwn::class_record(R, cls, p0, e0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_bwa_node_class(RecCols R, uint8_t* cls, int32_t* p0, int32_t* e0) { bwn::class_record(R, cls, p0, e0, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ __launch_bounds__(256) void k_bwa_node_tile_max(bwn::Keys K, const uint8_t* cls, int64_t ntiles, long long* tmax) {
     const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per tile
     if (tile >= ntiles) return;
@@ -5511,9 +5506,6 @@ __global__ __launch_bounds__(256) void k_bwa_node_run(bwn::Tab T, bwn::Par P, co
 __global__ __launch_bounds__(256) void k_bwa_node_gather(int32_t np, int32_t* report, const int32_t* at, const int32_t* seeds, int32_t* out) { bwn::gather_seeds(np, report, at, seeds, out, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
 struct FBwnSeeds { const int32_t* report; __device__ int operator()(int64_t k) const { return report[k * bwn::REPORT + bwn::R_SEEDS]; } };
 struct FBwnCls { const uint8_t* cls; uint8_t mask, want; __device__ int operator()(int64_t i) const { return (cls[i] & mask) == want ? 1 : 0; } };
-static_assert(bwn::AUX_MULTI == SQ_AUX_MULTI && bwn::AUX_LOWPHRED == SQ_AUX_LOWPHRED, "sq_bwa_nodes.inc restates these");
-static_assert((int)bwn::REPORT == (int)BNR_ROW && (int)bwn::R_SPARE == (int)BNR_SLICE && (int)bwn::R_BITS == (int)BNR_BITS && (int)bwn::R_SEEDS == (int)BNR_SEEDS && (int)bwn::R_MARKS_CLOSED == (int)BNR_MARKS_CLOSED &&
-              (int)bwn::R_MINPOS_OTH == (int)BNR_MINPOS_OTH && (int)bwn::R_READS == (int)BNR_READS, "the report row of sq_bwa_nodes.inc as sq_bwa.cpp reads it");
 
 // The stream loop of BuildNode_BWA over the resident table of a --bwa batch.  out.fallback (with out.why): nothing of `out` is valid and the
 // caller takes the host automaton -- the table is not resident, the passing records are not sorted by (RefID, pos), a slice of a stretch
@@ -5527,21 +5519,21 @@ int dev_bwa_seed_nodes(sq_ctx* c, int read_len, const int32_t rl5[5], BwaNodesOu
     hipStream_t s = c->stream;
     const int64_t n = D.n;
     if (n == 0) {  // (one empty stretch)
-        out.cut = {0, 0}; out.dis_in = {0}; out.report.assign(BNR_ROW, 0);
-        out.report[BNR_RL] = read_len; out.report[BNR_MARK_START] = -1; out.report[BNR_MARK_CHR] = -1; out.report[BNR_BITS] = 4; out.report[BNR_MINPOS_DIS] = INT32_MAX; out.report[BNR_MINPOS_OTH] = INT32_MAX;
+        out.cut = {0, 0}; out.dis_in = {0}; out.report.assign(bwn::REPORT, 0);
+        bwn::empty_report(out.report.data(), read_len);
         return SQ_OK;
     }
     if (n >= 0x7ffffff0ll) return back("more than 2^31 records");
-#define BWN_RESERVE(buf, count) do { if ((buf).reserve((size_t)(count)) != hipSuccess) { (void)hipGetLastError(); return back("a device buffer could not be had (SQ_E_CAPACITY)"); } } while (0)
+    const char* const no_buffer = "a device buffer could not be had (SQ_E_CAPACITY)";
     const int64_t ntiles = (n + bwn::TILE_RECS - 1) / bwn::TILE_RECS;
     const size_t n1 = (size_t)n + 1;
-    BWN_RESERVE(D.bwn_cls, n + 4); BWN_RESERVE(D.bwn_rec, 2 * (size_t)n + 3 * n1 + 4); BWN_RESERVE(D.bwn_tiles, 4 * (size_t)ntiles + 4); BWN_RESERVE(D.bwn_dlist, n + 16);
+    if (!(D.bwn_cls.try_reserve(n + 4) && D.bwn_rec.try_reserve(2 * (size_t)n + 3 * n1 + 4) && D.bwn_tiles.try_reserve(4 * (size_t)ntiles + 4) && D.bwn_dlist.try_reserve(n + 16))) return back(no_buffer);
     int32_t *p0 = D.bwn_rec.p, *e0 = p0 + n, *at_cut = e0 + n, *drank = at_cut + n1, *crank = drank + n1;
     long long *tmax = D.bwn_tiles.p, *front = tmax + 2 * ntiles;
     uint32_t *dlist = D.bwn_dlist.p, *flags = dlist + n;  // flags[0]: the kernels' flag word
     HIPCHK(hipMemsetAsync(flags, 0, 16 * 4, s));
     const RecView V = D.view();
-    const bwn::Recs R{n, V.refid, V.pos, V.mrefid, V.mpos, V.flag, V.totlen, V.mapq, V.aux, V.blk_off, V.b_refpos, V.b_matchref, V.b_readpos, V.b_matchread};
+    const RecCols R = V.cols();
     const bwn::Keys K{n, V.refid, V.pos, e0};
     const dim3 tgrid((unsigned)((ntiles + 3) / 4));
     { EvTimer t(c, "k_bwa_node_class", 40.0 * n); hipLaunchKernelGGL(k_bwa_node_class, grid_for(n, 256), dim3(256), 0, s, R, D.bwn_cls.p, p0, e0); }
@@ -5563,11 +5555,10 @@ int dev_bwa_seed_nodes(sq_ctx* c, int read_len, const int32_t rl5[5], BwaNodesOu
     if (h[3] & bwn::FLAG_UNSORTED) return back("the passing records are not sorted by (RefID, pos)");
     const int64_t n_cut = h[0], nd = h[1], nc = h[2], np = n_cut + 1;
     if (n_cut > n || nd > n || nc > n) return fail(c, SQ_E_ARG, "internal: a count of the --bwa node stage is larger than the table");
-    const int64_t seed_slots = 8 * nd + 2 * nc + 4 * np, margin_slots = 2 * nd + nc;
+    const int64_t seed_slots = bwn::seed_slots(nd, nc, np), margin_slots = bwn::margin_slots(nd, nc);
     if (3 * seed_slots >= 0x7fffffffll) return back("more seed slots than the route holds");
-    // cut (np + 1) | has | dr | dis_in | report (BNR_ROW per stretch)
-    BWN_RESERVE(D.bwn_str, (size_t)np * (4 + BNR_ROW) + 8); BWN_RESERVE(D.bwn_margins, margin_slots + 4); BWN_RESERVE(D.bwn_seeds, 3 * seed_slots + 4);
-#undef BWN_RESERVE
+    // cut (np + 1) | has | dr | dis_in | report (bwn::REPORT per stretch)
+    if (!(D.bwn_str.try_reserve((size_t)np * (4 + bwn::REPORT) + 8) && D.bwn_margins.try_reserve(margin_slots + 4) && D.bwn_seeds.try_reserve(3 * seed_slots + 4))) return back(no_buffer);
     int32_t *cut = D.bwn_str.p, *has = cut + np + 1, *dr = has + np, *dis_in = dr + np, *report = dis_in + np;
     const bwn::Tab T{n, V.refid, V.pos, V.totlen, D.bwn_cls.p, p0, e0, dlist, drank, crank};
     bwn::Par P;
@@ -5589,14 +5580,14 @@ int dev_bwa_seed_nodes(sq_ctx* c, int read_len, const int32_t rl5[5], BwaNodesOu
     HIPCHK(hipStreamSynchronize(s));
     const int64_t total = h[4];
     if (total > seed_slots) return fail(c, SQ_E_ARG, "internal: more seeds than slots in the --bwa node stage");
-    if (D.bwn_margins.reserve(margin_slots + 4 + 3 * (size_t)total) != hipSuccess) { (void)hipGetLastError(); return back("a device buffer could not be had (SQ_E_CAPACITY)"); }
+    if (!D.bwn_margins.try_reserve(margin_slots + 4 + 3 * (size_t)total)) return back(no_buffer);
     int32_t* strung = D.bwn_margins.p;  // (the margins are done with)
     { EvTimer t(c, "k_bwa_node_gather", 24.0 * total + 12.0 * np); hipLaunchKernelGGL(k_bwa_node_gather, grid_for(np, 256), dim3(256), 0, s, (int32_t)np, report, has, D.bwn_seeds.p, strung); }
-    out.cut.resize((size_t)np + 1); out.dis_in.resize((size_t)np); out.report.resize((size_t)np * BNR_ROW); out.seeds3.resize(3 * (size_t)total);
-    { EvTimer t(c, "bwa_node_download", 4.0 * (np + 1) + 4.0 * np * (1 + BNR_ROW) + 12.0 * total);
+    out.cut.resize((size_t)np + 1); out.dis_in.resize((size_t)np); out.report.resize((size_t)np * bwn::REPORT); out.seeds3.resize(3 * (size_t)total);
+    { EvTimer t(c, "bwa_node_download", 4.0 * (np + 1) + 4.0 * np * (1 + bwn::REPORT) + 12.0 * total);
       HIPCHK(hipMemcpyAsync(out.cut.data(), cut, ((size_t)np + 1) * 4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(out.dis_in.data(), dis_in, (size_t)np * 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(out.report.data(), report, (size_t)np * BNR_ROW * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(out.report.data(), report, (size_t)np * bwn::REPORT * 4, hipMemcpyDeviceToHost, s));
       if (total) HIPCHK(hipMemcpyAsync(out.seeds3.data(), strung, 3 * (size_t)total * 4, hipMemcpyDeviceToHost, s)); }
     HIPCHK(hipStreamSynchronize(s));
     return SQ_OK;
@@ -5610,10 +5601,6 @@ __global__ __launch_bounds__(256) void k_seg_run(sgs::Tab X, int32_t* nodes, int
     if (a >= X.na) return;
     sgs::run_stretch(X, (wv::lds_u32*)margins[threadIdx.x >> 6], nodes, report, a);
 }
-static_assert(sizeof(sgs::Rec) == sizeof(StreamRec) && offsetof(sgs::Rec, flags) == offsetof(StreamRec, flags) && offsetof(sgs::Rec, fb_readpos) == offsetof(StreamRec, fb_readpos), "sgs::Rec is StreamRec");
-static_assert(sgs::W_CONC == SR_CONC && sgs::W_PART == SR_PART && sgs::W_REV == SR_REV, "sq_segment_stage.inc restates these");
-static_assert((int)sgs::REPORT == (int)SGR_ROW && (int)sgs::R_EXT == (int)SGR_EXT && (int)sgs::R_SENS == (int)SGR_SENS && (int)sgs::R_MMAX == (int)SGR_MMAX && (int)sgs::SENS_CAP == 4 && (int)sgs::STRETCH == (int)SGT_ROW &&
-              (int)sgs::S_NODE_CAP == (int)SGT_NODE_CAP && (int)sgs::F_EXIST == (int)SGF_EXIST && (int)sgs::F_CAPACITY == (int)SGF_CAPACITY && (int)sgs::F_M_FULL == (int)SGF_M_FULL, "the rows of sq_segment_stage.inc as sq_segment.cpp reads them");
 
 bool dev_segment_recs_resident(const sq_ctx* c, int64_t n_recs) { return c->dev && n_recs > 0 && c->dev->srec_n == n_recs; }
 
@@ -5628,22 +5615,21 @@ int dev_segment_run(sq_ctx* c, const SegDevTables& T, bool recs_on_device, uint6
     hipStream_t s = c->stream;
     const size_t na = (size_t)T.na, ncl = (size_t)T.ncl;
     if (na == 0) return SQ_OK;
-    if (T.stretch.size() != na * SGT_ROW || T.d4.size() != 4 * ((size_t)T.nd + 1) || T.cl4.size() != 4 * ncl || T.part2.size() != 2 * (size_t)T.npart || T.rest_off.size() != ncl + 1 || T.trigger.size() != ncl ||
+    if (T.stretch.size() != na * sgs::STRETCH || T.d4.size() != 4 * ((size_t)T.nd + 1) || T.cl4.size() != 4 * ncl || T.part2.size() != 2 * (size_t)T.npart || T.rest_off.size() != ncl + 1 || T.trigger.size() != ncl ||
         T.rest_pos.size() != T.rest_len.size() || (ncl && (size_t)T.rest_off[ncl] != T.rest_pos.size()) || !T.recs || T.n_recs <= 0)
         return fail(c, SQ_E_ARG, "internal: the tables of the segmentation stage do not fit together");
-#define SEG_RESERVE(buf, count) do { if ((buf).reserve((size_t)(count)) != hipSuccess) { (void)hipGetLastError(); fallback = true; return SQ_OK; } } while (0)
     const size_t n_static = T.d4.size() + T.part2.size() + T.cl4.size() + 4;
     const size_t n_rest = T.rest_pos.size();
-    const size_t n_pass = (ncl + 1) + 2 * n_rest + ncl + na * SGT_ROW + 4;
-    const size_t n_out = na * SGR_ROW + 3 * (size_t)T.node_slots + 4;
+    const size_t n_pass = (ncl + 1) + 2 * n_rest + ncl + na * sgs::STRETCH + 4;
+    const size_t n_out = na * sgs::REPORT + 3 * (size_t)T.node_slots + 4;
     const bool have_static = static_key != 0 && D.seg_key == static_key && D.seg_static.p && D.seg_static.cap >= n_static;
-    if (!have_static) { D.seg_key = 0; SEG_RESERVE(D.seg_static, n_static); }
-    SEG_RESERVE(D.seg_pass, n_pass); SEG_RESERVE(D.seg_out, n_out);
-    if (!recs_on_device) { D.srec_n = -1; SEG_RESERVE(D.srec, T.n_recs); }
-#undef SEG_RESERVE
+    auto back = [&]() { fallback = true; return SQ_OK; };
+    if (!have_static) { D.seg_key = 0; if (!D.seg_static.try_reserve(n_static)) return back(); }
+    if (!(D.seg_pass.try_reserve(n_pass) && D.seg_out.try_reserve(n_out))) return back();
+    if (!recs_on_device) { D.srec_n = -1; if (!D.srec.try_reserve(T.n_recs)) return back(); }
     int32_t *d4 = D.seg_static.p, *part2 = d4 + T.d4.size(), *cl4 = part2 + T.part2.size();
     int32_t *rest_off = D.seg_pass.p, *rest_pos = rest_off + ncl + 1, *rest_len = rest_pos + n_rest, *trigger = rest_len + n_rest, *stretch = trigger + ncl;
-    int32_t *report = D.seg_out.p, *nodes = report + na * SGR_ROW;
+    int32_t *report = D.seg_out.p, *nodes = report + na * sgs::REPORT;
     {
         EvTimer t(c, "seg_upload", 4.0 * (have_static ? 0 : n_static) + 4.0 * n_pass + (recs_on_device ? 0.0 : 24.0 * T.n_recs));
         if (!have_static) {
@@ -5654,20 +5640,20 @@ int dev_segment_run(sq_ctx* c, const SegDevTables& T, bool recs_on_device, uint6
         HIPCHK(hipMemcpyAsync(rest_off, T.rest_off.data(), (ncl + 1) * 4, hipMemcpyHostToDevice, s));
         if (n_rest) { HIPCHK(hipMemcpyAsync(rest_pos, T.rest_pos.data(), n_rest * 4, hipMemcpyHostToDevice, s)); HIPCHK(hipMemcpyAsync(rest_len, T.rest_len.data(), n_rest * 4, hipMemcpyHostToDevice, s)); }
         if (ncl) HIPCHK(hipMemcpyAsync(trigger, T.trigger.data(), ncl * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(stretch, T.stretch.data(), na * SGT_ROW * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(stretch, T.stretch.data(), na * sgs::STRETCH * 4, hipMemcpyHostToDevice, s));
         if (!recs_on_device) HIPCHK(hipMemcpyAsync(D.srec.p, T.recs, (size_t)T.n_recs * sizeof(StreamRec), hipMemcpyHostToDevice, s));
     }
     HIPCHK(hipStreamSynchronize(s));  // (the sources are pageable)
     if (static_key != 0) D.seg_key = static_key;
     sgs::Tab X;
-    X.recs = (const sgs::Rec*)D.srec.p; X.RL = T.RL; X.nd = T.nd; X.ncl = T.ncl; X.npart = T.npart; X.na = T.na; X.K_eff = T.K_eff;
+    X.recs = D.srec.p; X.RL = T.RL; X.nd = T.nd; X.ncl = T.ncl; X.npart = T.npart; X.na = T.na; X.K_eff = T.K_eff;
     X.d4 = d4; X.part2 = part2; X.cl4 = cl4; X.rest_off = rest_off; X.rest_pos = rest_pos; X.rest_len = rest_len; X.trigger = trigger; X.stretch = stretch;
     { EvTimer t(c, "k_seg_run", 24.0 * T.n_recs + 16.0 * T.nd + 4.0 * n_out);
       hipLaunchKernelGGL(k_seg_run, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, s, X, nodes, report); }
     HIPCHK(hipGetLastError());
-    out.report.resize(na * SGR_ROW); out.nodes3.resize(3 * (size_t)T.node_slots);
+    out.report.resize(na * sgs::REPORT); out.nodes3.resize(3 * (size_t)T.node_slots);
     { EvTimer t(c, "seg_download", 4.0 * (n_out - 4));
-      HIPCHK(hipMemcpyAsync(out.report.data(), report, na * SGR_ROW * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(out.report.data(), report, na * sgs::REPORT * 4, hipMemcpyDeviceToHost, s));
       if (T.node_slots) HIPCHK(hipMemcpyAsync(out.nodes3.data(), nodes, 3 * (size_t)T.node_slots * 4, hipMemcpyDeviceToHost, s)); }
     HIPCHK(hipStreamSynchronize(s));
     return SQ_OK;

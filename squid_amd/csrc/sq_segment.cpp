@@ -936,21 +936,21 @@ const SegDevTables* segment_device_tables(const sq_ctx* c, SegPlan& plan) {
     if (T.rest_off.size() != ncl + 1) T.rest_off.assign(ncl + 1, 0);
     const std::vector<int32_t>& Z = plan.sup.zidx;
     const int nz = (int)Z.size();
-    T.stretch.resize(na * SGT_ROW);
+    T.stretch.resize(na * sgs::STRETCH);
     int64_t slots = 0;
     T.longest = 0;
     for (size_t a = 0; a < na; ++a) {
         const int j = plan.active[a];
-        int32_t* r = T.stretch.data() + a * SGT_ROW;
+        int32_t* r = T.stretch.data() + a * sgs::STRETCH;
         const int64_t lo = j == 0 ? -1 : Z[j - 1], hi = j < nz ? Z[j] : plan.K_eff;
         if (plan.shift[a] > INT32_MAX || plan.shift[a] < INT32_MIN) return nullptr;
         // a cluster seldom emits more than a node or two: four per cluster the stretch consumes, and four more
         const int64_t kn = a + 1 < na ? plan.first_cluster[a + 1] : (int64_t)ncl;
         const int64_t cap = 4 * (kn - plan.first_cluster[a]) + 4;
-        r[SGT_LO] = (int32_t)lo; r[SGT_HI] = (int32_t)hi; r[SGT_KC] = plan.first_cluster[a]; r[SGT_SHIFT] = (int32_t)plan.shift[a];
-        r[SGT_OCHR] = j < nz ? plan.sup.z_ochr[j] : 0; r[SGT_ORIGHT] = j < nz ? plan.sup.z_oright[j] : 0;
+        r[sgs::S_LO] = (int32_t)lo; r[sgs::S_HI] = (int32_t)hi; r[sgs::S_KC] = plan.first_cluster[a]; r[sgs::S_SHIFT] = (int32_t)plan.shift[a];
+        r[sgs::S_OCHR] = j < nz ? plan.sup.z_ochr[j] : 0; r[sgs::S_ORIGHT] = j < nz ? plan.sup.z_oright[j] : 0;
         if (slots + cap >= 0x20000000ll) return nullptr;
-        r[SGT_NODE_OFF] = (int32_t)slots; r[SGT_NODE_CAP] = (int32_t)cap;
+        r[sgs::S_NODE_OFF] = (int32_t)slots; r[sgs::S_NODE_CAP] = (int32_t)cap;
         slots += cap;
         T.longest = std::max<int64_t>(T.longest, hi - lo);
     }
@@ -963,35 +963,35 @@ int segment_walk(sq_ctx* c, SegPlan& plan, const SegDevTables& T, const SegDevOu
     seeds.clear();
     W = SegWalk();
     const size_t na = plan.active.size();
-    if ((size_t)T.na != na || D.report.size() != na * SGR_ROW) return fail(c, SQ_E_ARG, "internal: the stretch reports do not belong to the plan");
+    if ((size_t)T.na != na || D.report.size() != na * sgs::REPORT) return fail(c, SQ_E_ARG, "internal: the stretch reports do not belong to the plan");
     W.stretches = (int64_t)na; W.longest = T.longest;
     std::string err;
     std::vector<Node> tmp;
     for (size_t a = 0; a < na; ++a) {
-        const int32_t* r = D.report.data() + a * SGR_ROW;
-        const int32_t* st = T.stretch.data() + a * SGT_ROW;
-        const int flags = r[SGR_FLAGS];
+        const int32_t* r = D.report.data() + a * sgs::REPORT;
+        const int32_t* st = T.stretch.data() + a * sgs::STRETCH;
+        const int flags = r[sgs::R_FLAGS];
         const bool have = !seeds.empty();
-        bool ok = !(flags & SGF_CAPACITY);
-        if (flags & SGF_CAPACITY) ++W.flagged;
-        if (flags & SGF_M_FULL) ++W.flagged_margins;
-        const int nsens = std::min(r[SGR_NSENS], 4);
-        if (ok && !have) ok = !(flags & SGF_EXIST);  // (without a node every other comparison comes out as the guess says)
+        bool ok = !(flags & sgs::F_CAPACITY);
+        if (flags & sgs::F_CAPACITY) ++W.flagged;
+        if (flags & sgs::F_M_FULL) ++W.flagged_margins;
+        const int nsens = std::min(r[sgs::R_NSENS], sgs::SENS_CAP);
+        if (ok && !have) ok = !(flags & sgs::F_EXIST);  // (without a node every other comparison comes out as the guess says)
         else if (ok) {
             const Node& b = seeds.back();
             const int end = b.pos + b.len;
-            if (flags & SGF_CONSULTED) ok = b.chr < r[SGR_MINCHR] || (b.chr == r[SGR_MINCHR] && end <= r[SGR_BOUND]);
-            for (int k = 0; k < nsens; ++k) if (r[SGR_SENS + k] == end) { ok = false; ++W.sens_hits; }
+            if (flags & sgs::F_CONSULTED) ok = b.chr < r[sgs::R_MINCHR] || (b.chr == r[sgs::R_MINCHR] && end <= r[sgs::R_BOUND]);
+            for (int k = 0; k < nsens; ++k) if (r[sgs::R_SENS + k] == end) { ok = false; ++W.sens_hits; }
         }
         if (ok) {
             if (!have) ++W.leading_kept;  // (kept with no node in front: valid with and without one)
             W.sens += nsens;
-            const int n = r[SGR_NODES];
-            if (n > st[SGT_NODE_CAP] || (size_t)(st[SGT_NODE_OFF] + n) * 3 > D.nodes3.size()) return fail(c, SQ_E_ARG, "internal: a stretch reports more nodes than its slice holds");
-            const int32_t* q = D.nodes3.data() + 3 * (size_t)st[SGT_NODE_OFF];
+            const int n = r[sgs::R_NODES];
+            if (n > st[sgs::S_NODE_CAP] || (size_t)(st[sgs::S_NODE_OFF] + n) * 3 > D.nodes3.size()) return fail(c, SQ_E_ARG, "internal: a stretch reports more nodes than its slice holds");
+            const int32_t* q = D.nodes3.data() + 3 * (size_t)st[sgs::S_NODE_OFF];
             for (int i = 0; i < n; ++i) seeds.push_back(Node{q[3 * i], q[3 * i + 1], q[3 * i + 2], 0, 0.0});
             if (n) ++W.kept_with_nodes;
-            for (int k = 0; k < 3; ++k) W.ext[k] += r[SGR_EXT + k];
+            for (int k = 0; k < 3; ++k) W.ext[k] += r[sgs::R_EXT + k];
             continue;
         }
         ++W.again;

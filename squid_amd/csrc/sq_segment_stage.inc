@@ -23,24 +23,12 @@
 // (step 1) finds its first failing element by ballot; the second one depends on concord0pos through its break and walks element by element.
 #pragma once
 #include "sq_wave.h"
+#include "sq_stage_layout.h"
 #ifndef SGS_TRACE
 #define SGS_TRACE(kind, value) ((void)0)  // (the CPU harness counts what its cases contained through these; nothing on the device)
 #define SGS_TRACE_WINDOWS(S) ((void)0)
 #endif
 namespace sgs {
-constexpr int THRESH = 3, NEAR = 60;  // thresh, thresh * 20 (SegmentGraph.cpp:286)
-constexpr int M_CAP = 1024;           // entries of one margin list (a power of two: the sort pads to it)
-constexpr int SENS_CAP = 4;
-enum : uint8_t { W_CONC = 2, W_PART = 4, W_REV = 8, W_MASK = W_CONC | W_PART, W_C = W_CONC, W_P = W_CONC | W_PART };  // SR_* of sq_internal.h
-// the report row of one stretch
-enum { R_FLAGS = 0, R_NODES, R_MINCHR, R_BOUND, R_NSENS, R_SENS, R_EXT = R_SENS + SENS_CAP, R_CLUSTERS = R_EXT + 3, R_SUBS, R_MMAX, R_SPARE, REPORT };
-enum : int32_t { F_CONSULTED = 1, F_EXIST = 2, F_M_FULL = 4, F_NODES_FULL = 8, F_SENS_FULL = 16, F_GUARD = 32, F_CAPACITY = F_M_FULL | F_NODES_FULL | F_SENS_FULL | F_GUARD };
-// one row per active stretch: kept indices (lo, hi] (lo = -1: the head of the stream; hi = K_eff: the stream ends inside), its first cluster,
-// kept index that recs[0] would have, the running (otherChr, otherright) in front of record hi, where its nodes go and how many fit
-enum { S_LO = 0, S_HI, S_KC, S_SHIFT, S_OCHR, S_ORIGHT, S_NODE_OFF, S_NODE_CAP, STRETCH };
-enum { T_MARGIN = 0, T_SUB, T_DENSE, T_REST_FAIL, T_CHR_CHANGE, T_CLIP, T_BLOCKS };  // SGS_TRACE kinds
-
-struct Rec { int32_t refid, pos, fb_refpos, fb_matchref; uint16_t fb_readpos; uint8_t flags, nrest; uint32_t rest_off; };  // StreamRec
 struct Tab {
     const Rec* recs;
     int32_t RL, nd, ncl, npart, na, K_eff;

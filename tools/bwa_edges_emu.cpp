@@ -34,8 +34,7 @@ Emulated emulate(const HostBatch& hb, const std::vector<Node>& nodes, const chs:
     std::vector<int32_t> nchr, npos, nlen;
     for (const Node& n : nodes) { nchr.push_back(n.chr); npos.push_back(n.pos); nlen.push_back(n.len); }
     const chs::Nodes N{(int32_t)nodes.size(), nchr.data(), npos.data(), nlen.data()};
-    const bwe::Recs R{nf, hb.refid.data(), hb.pos.data(), hb.mrefid.data(), hb.mpos.data(), hb.flag.data(), hb.totlen.data(), hb.mapq.data(), hb.aux.data(), hb.blk_off.data(),
-                      hb.b_refpos.data(), hb.b_matchref.data(), hb.b_readpos.data(), hb.b_matchread.data()};
+    const RecCols R = hb.cols();
     std::vector<uint8_t> meta((size_t)nf, 0xff), bits((size_t)nf, 0xff), low((size_t)nf, 0), cls((size_t)nf + 1, 0);
     std::vector<int32_t> cnt((size_t)nf, -1), atot((size_t)nf, 0), btot((size_t)nf, 0);
     std::vector<uint32_t> off((size_t)nf + 1, 0), na((size_t)nf, 0);

@@ -17,8 +17,6 @@
 #include <random>
 using namespace sq;
 
-static_assert((int)bwn::REPORT == (int)BNR_ROW && (int)bwn::R_SPARE == (int)BNR_SLICE && (int)bwn::R_BITS == (int)BNR_BITS && (int)bwn::R_SEEDS == (int)BNR_SEEDS, "the report row");
-
 namespace {
 struct WaveArg {
     const bwn::Keys* K; uint8_t* cls; int64_t tile, ntiles; long long *tmax, *front; int rl_final; uint32_t* flags;
@@ -36,12 +34,11 @@ void emulate(const HostBatch& hb, int read_len, const int32_t rl5[5], BwaNodesOu
     cover_fails = 0; flag_word = 0;
     const int64_t n = (int64_t)hb.size();
     if (n == 0) {
-        D.cut = {0, 0}; D.dis_in = {0}; D.report.assign(BNR_ROW, 0);
-        D.report[BNR_RL] = read_len; D.report[BNR_MARK_START] = -1; D.report[BNR_MARK_CHR] = -1; D.report[BNR_BITS] = 4; D.report[BNR_MINPOS_DIS] = INT32_MAX; D.report[BNR_MINPOS_OTH] = INT32_MAX;
+        D.cut = {0, 0}; D.dis_in = {0}; D.report.assign(bwn::REPORT, 0);
+        bwn::empty_report(D.report.data(), read_len);
         return;
     }
-    const bwn::Recs R{n, hb.refid.data(), hb.pos.data(), hb.mrefid.data(), hb.mpos.data(), hb.flag.data(), hb.totlen.data(), hb.mapq.data(), hb.aux.data(), hb.blk_off.data(),
-                      hb.b_refpos.data(), hb.b_matchref.data(), hb.b_readpos.data(), hb.b_matchread.data()};
+    const RecCols R = hb.cols();
     std::vector<uint8_t> cls((size_t)n + 4, 0xff);
     std::vector<int32_t> p0((size_t)n, INT32_MIN), e0((size_t)n, INT32_MIN), at_cut((size_t)n + 1, -7), drank((size_t)n + 1, -7), crank((size_t)n + 1, -7);
     for (int64_t r = n; r-- > 0;) bwn::class_record(R, cls.data(), p0.data(), e0.data(), r);
@@ -63,8 +60,8 @@ void emulate(const HostBatch& hb, int read_len, const int32_t rl5[5], BwaNodesOu
     }
     at_cut[(size_t)n] = n_cut; drank[(size_t)n] = nd; crank[(size_t)n] = nc;
     const int32_t np = n_cut + 1;
-    const int64_t seed_slots = 8ll * nd + 2ll * nc + 4ll * np, margin_slots = 2ll * nd + nc;
-    std::vector<int32_t> cut((size_t)np + 1, -7), has((size_t)np, -7), dr((size_t)np, -7), dis_in((size_t)np, -7), report((size_t)np * BNR_ROW, -7), margins((size_t)margin_slots + 4, INT32_MIN),
+    const int64_t seed_slots = bwn::seed_slots(nd, nc, np), margin_slots = bwn::margin_slots(nd, nc);
+    std::vector<int32_t> cut((size_t)np + 1, -7), has((size_t)np, -7), dr((size_t)np, -7), dis_in((size_t)np, -7), report((size_t)np * bwn::REPORT, -7), margins((size_t)margin_slots + 4, INT32_MIN),
         seeds(3 * (size_t)seed_slots + 4, INT32_MIN);
     std::vector<uint32_t> dlist((size_t)nd + 1, ~0u);
     for (int64_t r = n; r-- > 0;) bwn::scatter(n, cls.data(), at_cut.data(), drank.data(), n_cut, cut.data(), dlist.data(), r);
@@ -80,7 +77,7 @@ void emulate(const HostBatch& hb, int read_len, const int32_t rl5[5], BwaNodesOu
     if (flags[0]) { D.fallback = true; D.why = "a slice or a bound"; return; }
     std::vector<int32_t> at((size_t)np, 0);
     int32_t total = 0;
-    for (int32_t k = 0; k < np; ++k) { at[(size_t)k] = total; total += report[(size_t)k * BNR_ROW + BNR_SEEDS]; cover_fails += report[(size_t)k * BNR_ROW + bwn::R_COVER_FAILS]; }
+    for (int32_t k = 0; k < np; ++k) { at[(size_t)k] = total; total += report[(size_t)k * bwn::REPORT + bwn::R_SEEDS]; cover_fails += report[(size_t)k * bwn::REPORT + bwn::R_COVER_FAILS]; }
     D.seeds3.assign(3 * (size_t)total + 1, INT32_MIN);
     for (int64_t k = np; k-- > 0;) bwn::gather_seeds(np, report.data(), at.data(), seeds.data(), D.seeds3.data(), k);
     D.seeds3.resize(3 * (size_t)total);

@@ -30,12 +30,12 @@ struct NodeTab {
         N.n = n; N.n_ref = n_ref; N.chr = chr.data(); N.pos = pos.data(); N.len = len.data(); N.chr_start = chr_start.data(); N.fine = nullptr; N.fine_off = nullptr;
         if (!with_fine) return;
         fine_off.assign((size_t)n_ref + 1, 0);
-        for (int k = 0; k < n_ref; ++k) fine_off[(size_t)k + 1] = fine_off[(size_t)k] + ((std::max(ref_len[(size_t)k], 1) + (1 << bws::FINE_SHIFT) - 1) >> bws::FINE_SHIFT) + 1;
+        for (int k = 0; k < n_ref; ++k) fine_off[(size_t)k + 1] = fine_off[(size_t)k] + ((std::max(ref_len[(size_t)k], 1) + (1 << NODE_FINE_SHIFT) - 1) >> NODE_FINE_SHIFT) + 1;
         fine.assign((size_t)fine_off[(size_t)n_ref] + 1, 0);
         for (int k = 0; k < n_ref; ++k)
             for (int g = fine_off[(size_t)k]; g < fine_off[(size_t)k + 1]; ++g) {
                 if (g == fine_off[(size_t)k + 1] - 1) { fine[(size_t)g] = chr_start[(size_t)k + 1] - 1; continue; }
-                const int p = (g - fine_off[(size_t)k]) << bws::FINE_SHIFT;
+                const int p = (g - fine_off[(size_t)k]) << NODE_FINE_SHIFT;
                 int lo = chr_start[(size_t)k], hi = chr_start[(size_t)k + 1];
                 while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (pos[(size_t)mid] <= p) lo = mid; else hi = mid; }
                 fine[(size_t)g] = lo;
@@ -356,19 +356,19 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> h_reads, h_look, h_names;
     bwa_reads_bytes(hb, h_reads); bwa_look_bytes(&c, h_look); bwa_name_bytes(&c, h_names);
     // the class kernel, lane by lane from the last record to the first: READS first (with the chromosome per block), then both bits behind the name test
-    const bws::Recs R{(int64_t)nrec, hb.refid.data(), hb.pos.data(), hb.mrefid.data(), hb.mpos.data(), hb.flag.data(), hb.mapq.data(), hb.aux.data(), hb.blk_off.data()};
+    const RecCols R = hb.cols();
     std::vector<uint8_t> cls(nrec + 1, 0xff);
     std::vector<int32_t> blk_chr(nblk + 1, -2);
     long bad = 0, n_reads = 0, n_p3 = 0, n_named = 0, n_left = 0, n_below = 0;
     for (int64_t r = (int64_t)nrec; r-- > 0;) bws::classify(R, c.P.min_mapqual, nullptr, cls.data(), blk_chr.data(), r);
     for (size_t r = 0; r < nrec; ++r) {
-        if (((cls[r] & bws::CLS_READS) != 0) != (h_reads[r] != 0)) { if (bad < 10) std::printf("   record %zu: READS bit %d, host %d\n", r, (cls[r] & bws::CLS_READS) != 0, (int)h_reads[r]); ++bad; }
+        if (((cls[r] & C_READS) != 0) != (h_reads[r] != 0)) { if (bad < 10) std::printf("   record %zu: READS bit %d, host %d\n", r, (cls[r] & C_READS) != 0, (int)h_reads[r]); ++bad; }
         for (uint32_t b = hb.blk_off[r]; b < hb.blk_off[r + 1]; ++b) if (blk_chr[b] != (h_reads[r] ? hb.refid[r] : -1)) { if (bad < 10) std::printf("   block %u: chromosome %d\n", b, blk_chr[b]); ++bad; }
     }
     for (int64_t r = (int64_t)nrec; r-- > 0;) bws::classify(R, c.P.min_mapqual, h_names.data(), cls.data(), nullptr, r);
     for (size_t r = 0; r < nrec; ++r) {
-        const bool reads = (cls[r] & bws::CLS_READS) != 0, p3 = (cls[r] & bws::CLS_P3) != 0;
-        if (reads != (h_reads[r] != 0) || p3 != (h_look[r] != 0) || (cls[r] & ~(bws::CLS_READS | bws::CLS_P3))) { if (bad < 10) std::printf("   record %zu: class %d, host READS %d / look %d\n", r, (int)cls[r], (int)h_reads[r], (int)h_look[r]); ++bad; }
+        const bool reads = (cls[r] & C_READS) != 0, p3 = (cls[r] & C_P3) != 0;
+        if (reads != (h_reads[r] != 0) || p3 != (h_look[r] != 0) || (cls[r] & ~(C_READS | C_P3))) { if (bad < 10) std::printf("   record %zu: class %d, host READS %d / look %d\n", r, (int)cls[r], (int)h_reads[r], (int)h_look[r]); ++bad; }
         n_reads += reads; n_p3 += p3; n_named += h_names[r];
         // of the host's READS records: the middle class (MAPQ below -mq: feeds Reads, not looked at by the breakpoint support), and the left-hand
         // records of a pair among the others

@@ -22,9 +22,6 @@ static void seg_trace_windows(const void* recs, int co, int po, int wend);
 #include "../squid_amd/csrc/sq_segment_stage.inc"
 using namespace sq;
 
-static_assert(sizeof(sgs::Rec) == sizeof(StreamRec) && offsetof(sgs::Rec, flags) == offsetof(StreamRec, flags), "sgs::Rec is StreamRec");
-static_assert((int)sgs::REPORT == (int)SGR_ROW && (int)sgs::STRETCH == (int)SGT_ROW && (int)sgs::R_NODES == (int)SGR_NODES, "the rows");
-
 namespace {
 struct Trace {
     long m2 = 0, m63 = 0, m64 = 0, m65 = 0, mcap = 0, mover = 0, w0 = 0, w1 = 0, w64 = 0, w65 = 0, big = 0, split = 0, dense_fired = 0, dense_split = 0, rest_fail = 0, chr_mark = 0, chr_walk = 0, clip_fwd = 0,
@@ -56,9 +53,9 @@ void w_run(void* p) { const WaveArg& a = *(const WaveArg*)p; sgs::run_stretch(*a
 
 // dev_segment_run, wave by wave
 void emulate(const SegDevTables& T, SegDevOut& D) {
-    D.report.assign((size_t)T.na * SGR_ROW, -7); D.nodes3.assign(3 * (size_t)T.node_slots + 3, INT32_MIN);
+    D.report.assign((size_t)T.na * sgs::REPORT, -7); D.nodes3.assign(3 * (size_t)T.node_slots + 3, INT32_MIN);
     sgs::Tab X;
-    X.recs = (const sgs::Rec*)T.recs; X.RL = T.RL; X.nd = T.nd; X.ncl = T.ncl; X.npart = T.npart; X.na = T.na; X.K_eff = T.K_eff;
+    X.recs = T.recs; X.RL = T.RL; X.nd = T.nd; X.ncl = T.ncl; X.npart = T.npart; X.na = T.na; X.K_eff = T.K_eff;
     X.d4 = T.d4.data(); X.part2 = T.part2.data(); X.cl4 = T.cl4.data(); X.rest_off = T.rest_off.data(); X.rest_pos = T.rest_pos.data(); X.rest_len = T.rest_len.data(); X.trigger = T.trigger.data();
     X.stretch = T.stretch.data();
     std::vector<uint32_t> M((size_t)sgs::M_CAP);
@@ -302,7 +299,7 @@ int main(int argc, char** argv) {
         for (int q = 0; q < 3; ++q) ext[q] += (long)h.walk.ext[q];
         no_block += in.n_disc == 0;
         for (int q = 0; q < ncl; ++q) never += cs.trigger[(size_t)q] >= K;
-        for (int a = 0; a < T->na; ++a) { const int32_t* r = T->stretch.data() + (size_t)a * SGT_ROW; single += r[SGT_HI] - r[SGT_LO] == 1; ends_inside += r[SGT_HI] == K; }
+        for (int a = 0; a < T->na; ++a) { const int32_t* r = T->stretch.data() + (size_t)a * sgs::STRETCH; single += r[sgs::S_HI] - r[sgs::S_LO] == 1; ends_inside += r[sgs::S_HI] == K; }
         if (cs.near_gap) near_again += (long)e.walk.again;
     }
     if (out) std::fclose(out);
