@@ -10,7 +10,7 @@ CXX ?= g++
 ARCH ?= gfx950
 B := build
 CSRC := squid_amd/csrc
-LIBSRC := $(CSRC)/sq_kernels.hip $(CSRC)/sq_bam.cpp $(CSRC)/sq_chimeric.cpp $(CSRC)/sq_segment.cpp $(CSRC)/sq_graph.cpp $(CSRC)/sq_order.cpp $(CSRC)/sq_post.cpp $(CSRC)/sq_bwa.cpp $(CSRC)/sq_junction.cpp $(CSRC)/sq_exchange.cpp $(CSRC)/sq_capi.cpp
+LIBSRC := $(CSRC)/sq_kernels.hip $(CSRC)/sq_bam.cpp $(CSRC)/sq_chimeric.cpp $(CSRC)/sq_segment.cpp $(CSRC)/sq_graph.cpp $(CSRC)/sq_order.cpp $(CSRC)/sq_post.cpp $(CSRC)/sq_bwa.cpp $(CSRC)/sq_junction.cpp $(CSRC)/sq_exchange.cpp $(CSRC)/sq_shard.cpp $(CSRC)/sq_build.cpp $(CSRC)/sq_capi.cpp
 
 all: $(B)/libsquid_hip.so $(B)/squid $(B)/squid_junction $(B)/squid_annotate $(B)/gen_synth_bam $(B)/squid_oracle $(B)/oracle_singlebamrec ref
 
@@ -19,7 +19,7 @@ all: $(B)/libsquid_hip.so $(B)/squid $(B)/squid_junction $(B)/squid_annotate $(B
 ref:
 	$(MAKE) -C oracle ref
 
-$(B)/libsquid_hip.so: $(LIBSRC) $(CSRC)/sq_internal.h $(CSRC)/sq_stage_layout.h $(CSRC)/sq_parsort.h $(CSRC)/sq_graph_kernels.inc $(CSRC)/sq_pass_kernels.inc $(CSRC)/sq_inflate_spec.inc $(CSRC)/sq_resolve.inc $(CSRC)/sq_chim_stage.inc $(CSRC)/sq_bwa_stage.inc $(CSRC)/sq_bwa_edges.inc $(CSRC)/sq_bwa_nodes.inc $(CSRC)/sq_segment_stage.inc $(CSRC)/sq_wave.h include/squid_hip.h
+$(B)/libsquid_hip.so: $(LIBSRC) $(CSRC)/sq_internal.h $(CSRC)/sq_shard.h $(CSRC)/sq_stage_layout.h $(CSRC)/sq_parsort.h $(CSRC)/sq_graph_kernels.inc $(CSRC)/sq_pass_kernels.inc $(CSRC)/sq_inflate_spec.inc $(CSRC)/sq_resolve.inc $(CSRC)/sq_chim_stage.inc $(CSRC)/sq_bwa_stage.inc $(CSRC)/sq_bwa_edges.inc $(CSRC)/sq_bwa_nodes.inc $(CSRC)/sq_segment_stage.inc $(CSRC)/sq_wave.h include/squid_hip.h
 	mkdir -p $(B)
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -shared -Wall -Wno-unused-function -o $@ $(LIBSRC) -lz -lpthread -ldl
 

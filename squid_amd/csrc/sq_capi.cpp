@@ -1,4 +1,4 @@
-// C-ABI entry points of libsquid_hip.so (include/squid_hip.h) and the stage pipeline behind them.
+// C-ABI entry points of libsquid_hip.so (include/squid_hip.h): the ingest and debug entry points; the pipelines behind sq_build_graph / sq_call_sv are sq_build.cpp.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -12,7 +12,6 @@
 
 #include "sq_internal.h"
 #include <malloc.h>
-#include "sq_parsort.h"
 
 namespace sq {
 
@@ -69,754 +68,7 @@ void GraphSnap::view(sq_graph* g) const {
     g->ind1 = ind1.data(); g->ind2 = ind2.data(); g->weight = weight.data(); g->groupweight = gweight.data(); g->head1 = h1.data(); g->head2 = h2.data();
 }
 
-int dev_breakpoint_support_exact(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& coverage);
-
-
-// ---- exchange payloads (chromosome-sharded runs): plain little-endian PODs appended to a byte vector
-struct Packer {
-    std::vector<uint8_t>& b;
-    explicit Packer(std::vector<uint8_t>& buf) : b(buf) { b.clear(); }
-    template <class T> void put(const T& v) { const uint8_t* p = (const uint8_t*)&v; b.insert(b.end(), p, p + sizeof(T)); }
-    template <class T> void put_vec(const std::vector<T>& v) { put<int64_t>((int64_t)v.size()); const uint8_t* p = (const uint8_t*)v.data(); b.insert(b.end(), p, p + v.size() * sizeof(T)); }
-};
-struct Unpacker {
-    const std::vector<uint8_t>& b; size_t at = 0; bool ok = true;
-    explicit Unpacker(const std::vector<uint8_t>& buf) : b(buf) {}
-    template <class T> T get() { T v{}; if (at + sizeof(T) > b.size()) { ok = false; return v; } std::memcpy(&v, b.data() + at, sizeof(T)); at += sizeof(T); return v; }
-    template <class T> void get_vec(std::vector<T>& v) {
-        int64_t n = get<int64_t>();
-        if (!ok || n < 0 || at + (size_t)n * sizeof(T) > b.size()) { ok = false; v.clear(); return; }
-        v.resize((size_t)n);
-        if (n) std::memcpy(v.data(), b.data() + at, (size_t)n * sizeof(T));
-        at += (size_t)n * sizeof(T);
-    }
-};
-enum : int32_t { X_DEDUP = 0x51a0, X_STREAM, X_SEEDS, X_GRAPH, X_BPSUP, X_OTHER };  // payload tags (a mismatch means the ranks are out of step)
-
-// locals of build_graph that have to survive an exchange
-struct GraphBuild {
-    int stage = 0;
-    std::shared_ptr<SegPlan> plan;
-    std::vector<Blk> disc;
-    int64_t n_break = 0;
-    int64_t trigger_last = 0;
-    std::vector<Node> seeds;
-    std::vector<Edge> raw, conc, before;  // before: the edges in front of FilterEdges (the filter is repeated when a depth decision was ambiguous)
-    std::vector<uint8_t> keep;          // KeepEdge of FilterbyInterleaving
-    std::vector<int32_t> sup, amb_plus, amb_minus;
-    std::vector<int64_t> sl;
-    bool tiny_boundary = false;
-    std::vector<int32_t> first_chr;   // sharded: chromosome of every rank's first kept record (-1: none)
-    // sharded seed exchange: this shard's seeds under the three possible pasts (see stage 3)
-    std::vector<Node> seedsA, seedsB, seedsC;
-    std::vector<int32_t> sensB;
-    bool hasC = false;
-    Node seedC{0, 0, 0, 0, 0.0};
-    std::future<double> clusters;     // segment_clusters running next to the record kernels
-    ~GraphBuild() { if (clusters.valid()) clusters.wait(); }  // (a pooled task's future does not wait by itself; the task writes into this object)
-};
-
-static int need_exchange(sq_ctx* c) {
-    c->x_pending = true; c->x_ready = false;
-    return SQ_NEED_EXCHANGE;
-}
-// the gathered payloads of the exchange that has just completed, or an error when the caller skipped it
-static int take_exchange(sq_ctx* c, int32_t tag) {
-    if (!c->x_ready || (int)c->xgot.size() != c->P.world_size) return fail(c, SQ_E_ARG, "sharded run: sq_exchange_unpack has not been called for the pending exchange");
-    c->x_ready = false;
-    for (const auto& v : c->xgot) { int32_t t = 0; if (v.size() < 4) return fail(c, SQ_E_ARG, "sharded run: short exchange payload"); std::memcpy(&t, v.data(), 4); if (t != tag) return fail(c, SQ_E_ARG, "sharded run: ranks are out of step (payload tag mismatch)"); }
-    return SQ_OK;
-}
-
-static void pack_seeds(sq_ctx* c, const GraphBuild& g) {
-    auto flat = [](const std::vector<Node>& v) { std::vector<int32_t> f; f.reserve(v.size() * 3); for (const Node& n : v) { f.push_back(n.chr); f.push_back(n.pos); f.push_back(n.len); } return f; };
-    Packer pk(c->xbuf);
-    pk.put<int32_t>(X_SEEDS);
-    pk.put_vec(flat(g.seedsA));
-    pk.put<int32_t>(c->shard.prior_kept ? 1 : 0);
-    pk.put_vec(flat(g.seedsB));
-    pk.put_vec(g.sensB);
-    pk.put<int32_t>(g.hasC ? 1 : 0);
-    pk.put<int32_t>(g.seedC.chr); pk.put<int32_t>(g.seedC.pos); pk.put<int32_t>(g.seedC.len);
-    pk.put_vec(flat(g.seedsC));
-}
-
-// CompressNode .. MultiplyDisEdges of the constructor (SegmentGraph.cpp:117-122), shared by the STAR and the --bwa path
-// SQUID_HOST_FILTERS: the edge filters and the node compression on the host (cross-check of the device route)
-static bool host_filters_env() { static const bool v = env_set("SQUID_HOST_FILTERS"); return v; }
-
-static int finish_graph(sq_ctx* c, bool host_filters) {
-    int rc;
-    {
-        HostClock hc(c, host_filters ? "host_compress" : "wall_compress");
-        rc = host_filters ? compress_nodes(c) : dev_compress_nodes(c);
-        if (rc) return rc;
-        if (c->keep_stages) c->snap[5].take(c->nodes, c->edges, nullptr);
-        rc = host_filters ? further_compress(c) : dev_further_compress(c);
-        if (rc == 2) rc = further_compress(c);  // a node with more discordant edges than the kernel's lists hold
-        if (rc) return rc;
-    }
-    rc = dev_connected_components(c, (int)c->nodes.size(), c->edges, c->label);
-    if (rc) return rc;
-    multiply_discordant(c, false);
-    c->snap[0].take(c->nodes, c->edges, &c->label);
-    c->graph_built = true;
-    c->gb.reset();
-    // ExactBreakpoint only needs the final graph and the trimmed fragments: start it now, sq_call_sv collects it
-    c->chim_s2_pending = false;
-    if (c->chim_s1_device) {  // the trimmed blocks are in HBM: the stage is queued on the stream behind the graph (sq_chim_stage.inc)
-        bool fb = false;
-        rc = dev_exact_breakpoints_start(c, fb);
-        if (rc) return rc;
-        if (!fb) { c->chim_s2_pending = true; return SQ_OK; }
-        c->timer.add("chim_device_fallback", 0, 0, 1);
-        if ((rc = dev_chim_download_trimmed(c))) return rc;  // (the host stage continues from the blocks as stage 1 left them)
-        c->chim_s1_device = false;
-    }
-    c->bp_early = std::make_shared<BPMap>();
-    c->bp_future = c->pool->submit([c]() {
-        const auto t0 = std::chrono::steady_clock::now();
-        const int r2 = exact_breakpoints(c, *c->bp_early);
-        c->bp_early_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return r2;
-    });
-    return SQ_OK;
-}
-
-// `squid --bwa`: BuildNode_BWA and RawEdges on the host over the decoded batch (sq_bwa.cpp), then the same edge reduction, filters,
-// compression and component labelling as the STAR path (SegmentGraph.cpp:104-124 with UsingSTAR == false).  Node depths are exact
-// here (no unstable sort in this mode's depth sweep), so the coverage-ratio test needs no bounds.
-static int build_graph_bwa(sq_ctx* c) {
-    HostClock wall(c, "wall_build_graph");
-    if (c->shard.on) return fail(c, SQ_E_ARG, "--bwa input is not chromosome-sharded");
-    c->graph_built = false; c->ordered = false;
-    c->depth_bounds = false; c->depth_ambiguous = false;
-    c->chim_s1_device = false;
-    std::vector<Edge> raw;
-    int rc = bwa_nodes_and_edges(c, raw);
-    if (rc) return rc;
-    // (counts.n_raw_edges: set by bwa_raw_edges -- the edges as the loop emitted them; `raw` arrives summed per stretch)
-    c->edges.clear();
-    { HostClock hc(c, "host_edge_reduce"); reduce_edges(raw, c->edges, c->pool ? std::min(c->pool->size() + 1, 32) : 1); }
-    c->counts.n_unique_edges = (int64_t)c->edges.size();
-    if (c->keep_stages) c->snap[2].take(c->nodes, c->edges, nullptr);
-    const bool host_filters = host_filters_env();
-    {
-        HostClock hc(c, host_filters ? "host_filters" : "wall_filters");
-        std::vector<uint8_t> keep;
-        if (host_filters) filter_by_weight(c); else if ((rc = dev_filter_by_weight(c))) return rc;
-        if (c->keep_stages) c->snap[3].take(c->nodes, c->edges, nullptr);
-        if (host_filters) filter_by_interleaving(c, keep); else if ((rc = dev_filter_by_interleaving(c, keep))) return rc;
-        if (host_filters) filter_edges(c, keep); else if ((rc = dev_filter_edges(c, keep))) return rc;
-        if (c->keep_stages) c->snap[4].take(c->nodes, c->edges, nullptr);
-    }
-    return finish_graph(c, host_filters);
-}
-
 static void drop_early_clusters(sq_ctx* c) { c->plan_early.reset(); c->disc_early.clear(); c->disc_early.shrink_to_fit(); c->clusters_early_ms = -1; }
-static int build_graph(sq_ctx* c) {
-    HostClock wall(c, "wall_build_graph");
-    Shard& sh = c->shard;
-    const int W = c->P.world_size, me = c->P.rank;
-    if (!c->gb) c->gb = std::make_shared<GraphBuild>();
-    GraphBuild& g = *c->gb;
-    int rc;
-    if (g.stage == 0) {
-        c->graph_built = false;
-        c->ordered = false;
-        // the cluster table only needs the chimeric fragments: build it on a second thread next to the record kernels
-        // (the table is a function of the chimeric fragments and ReadLen alone: built beside the ingest by sq_ingest_files, or by the first pass,
-        // and KEPT by the context until the fragments change -- a later pass over the same records, sq_reset and a new set of -w/-r/-a, takes
-        // it as it is; everything a pass writes into the plan is written again by the next one)
-        if (c->clusters_early_ms >= 0 && c->plan_early) {
-            g.plan = c->plan_early; g.disc = c->disc_early;
-            std::promise<double> done;
-            done.set_value(c->clusters_early_ms);
-            g.clusters = done.get_future();
-            c->clusters_early_ms = 0;  // (a second use costs nothing)
-        } else g.clusters = c->pool->submit([c, &g]() { const double ms = segment_clusters(c, g.plan, g.disc); c->plan_early = g.plan; c->disc_early = g.disc; c->clusters_early_ms = 0; return ms; });
-        int32_t last[4];
-        rc = dev_classify(c, sh.on ? last : nullptr);
-        if (rc) { (void)g.clusters.get(); return rc; }
-        g.stage = 1;
-        if (sh.on) {  // exchange 1: what the last passing records of every shard look like to ReadRec_t::Equal
-            Packer pk(c->xbuf);
-            pk.put<int32_t>(X_DEDUP);
-            for (int i = 0; i < 4; ++i) pk.put<int32_t>(last[i]);
-            return need_exchange(c);
-        }
-    }
-    if (g.stage == 1) {
-        if (sh.on) {
-            rc = take_exchange(c, X_DEDUP);
-            if (rc) return rc;
-            sh.dedup_mask = 0;
-            for (int r = 0; r < me; ++r) {
-                Unpacker u(c->xgot[r]);
-                u.get<int32_t>();
-                for (int p = 0; p < 2; ++p) {
-                    int32_t has = u.get<int32_t>(), empty = u.get<int32_t>();
-                    if (has) { if (empty) sh.dedup_mask &= ~(1 << p); else sh.dedup_mask |= 1 << p; }
-                }
-            }
-        }
-        const double cl_ms = g.clusters.get();  // (k_pass1 needs the cluster table up front: it reads the records once, for everything)
-        c->timer.add("host_cluster_table", cl_ms);
-        long long other_max = INT64_MIN;
-        int32_t first_kept[2] = {0, 0};
-        {
-            HostClock hc(c, "host_segment_prepare");
-            rc = segment_scan(c, *g.plan, sh.on, g.trigger_last, other_max, first_kept);
-            if (rc) return rc;
-        }
-        g.stage = 2;
-        if (sh.on) {  // exchange 2: size, first record, running other-pair and last-cluster trigger of every local stream
-            Packer pk(c->xbuf);
-            pk.put<int32_t>(X_STREAM);
-            pk.put<int64_t>(c->counts.n_kept_p1);
-            pk.put<int32_t>(first_kept[0]); pk.put<int32_t>(first_kept[1]);
-            pk.put<int64_t>(other_max);
-            pk.put<int64_t>(g.trigger_last);
-            return need_exchange(c);
-        }
-    }
-    if (g.stage == 2) {
-        if (sh.on) {
-            rc = take_exchange(c, X_STREAM);
-            if (rc) return rc;
-            std::vector<int64_t> K(W), tl(W), om(W);
-            std::vector<int32_t> fr(W), fp(W);
-            for (int r = 0; r < W; ++r) {
-                Unpacker u(c->xgot[r]);
-                u.get<int32_t>();
-                K[r] = u.get<int64_t>(); fr[r] = u.get<int32_t>(); fp[r] = u.get<int32_t>(); om[r] = u.get<int64_t>(); tl[r] = u.get<int64_t>();
-                if (!u.ok) return fail(c, SQ_E_ARG, "sharded run: malformed stream payload");
-            }
-            g.first_chr.assign(W, -1);
-            for (int r = 0; r < W; ++r) if (K[r] > 0) g.first_chr[r] = fr[r];
-            sh.kept_before = 0; sh.kept_total = 0; sh.prior_kept = false; sh.other_seed = INT64_MIN; sh.has_terminal = false;
-            for (int r = 0; r < W; ++r) {
-                if (r < me) { sh.kept_before += K[r]; if (K[r] > 0) { sh.prior_kept = true; sh.other_seed = std::max<long long>(sh.other_seed, om[r]); } }
-                if (r > me && K[r] > 0 && !sh.has_terminal) { sh.has_terminal = true; sh.term_refid = fr[r]; sh.term_pos = fp[r]; }
-                sh.kept_total += K[r];
-            }
-            // B12: the consumed prefix ends one record behind the trigger of the globally last cluster
-            if (g.trigger_last < 0) sh.n_break_global = std::min<int64_t>(sh.kept_total, 1);  // no discordant cluster at all
-            else {
-                int64_t T = sh.kept_total, off = 0;
-                for (int r = 0; r < W; ++r) { if (tl[r] >= 0 && tl[r] < K[r]) { T = off + tl[r]; break; } off += K[r]; }
-                sh.n_break_global = std::min<int64_t>(sh.kept_total, T + 2);
-            }
-        }
-        {
-            HostClock hc(c, "host_segment_prepare");
-            rc = segment_prepare(c, *g.plan, g.n_break);
-            if (rc) return rc;
-        }
-        c->counts.n_break = g.n_break;
-        bool seg_on_device = false;
-        if (c->seg_dev_on()) {  // (sq_segment_on_device: one wave per stretch, the host walks the reports; a plan too large comes back)
-            SegWalk W;
-            bool fb = false;
-            c->timer.add("segment_device_fallback", 0, 0, 0);
-            rc = segment_replay_device(c, *g.plan, g.seeds, W, fb);
-            if (rc) return rc;
-            if (fb) c->timer.add("segment_device_fallback", 0, 0, 1);
-            else {
-                seg_on_device = true;
-                c->timer.add("segment_stretches", 0, 0, W.stretches); c->timer.add("segment_stretches_run_again", 0, 0, W.again); c->timer.add("segment_longest_stretch", 0, 0, W.longest);
-                g.seedsA = g.seeds; g.seedsB.clear(); g.sensB.clear(); g.hasC = false;
-            }
-        }
-        if (!seg_on_device) {
-            HostClock hc(c, "host_segment_replay");
-            g.seedsB.clear(); g.sensB.clear(); g.hasC = false;
-            std::future<int> hypB;  // a shard that does not start the stream replays under both pasts, side by side
-            if (sh.on && sh.prior_kept) hypB = c->pool->submit([&]() { return segment_replay(c, *g.plan, g.seedsB, true, &g.sensB, nullptr); });
-            rc = segment_replay(c, *g.plan, g.seeds, false, nullptr, nullptr);
-            g.seedsA = g.seeds;
-            if (hypB.valid()) { const int rb = hypB.get(); if (!rc) rc = rb; }
-        }
-        if (rc) return rc;
-        g.stage = 3;
-        if (sh.on) { pack_seeds(c, g); return need_exchange(c); }
-    }
-    if (g.stage == 3) {
-        if (sh.on) {
-            rc = take_exchange(c, X_SEEDS);
-            if (rc) return rc;
-            // Seed nodes of all shards, resolved in rank order.  What a shard emits depends on the last node emitted before
-            // it: none (A); one on an earlier chromosome than the shard's records, then only its existence matters (B);
-            // or -- a discordant cluster in front of a chromosome's first kept record is processed by the shard before --
-            // one on the shard's own first chromosome, then the shard replays again behind exactly that node (C) and
-            // everybody exchanges once more.
-            std::vector<Node> all;
-            int redo = -1;
-            for (int r = 0; r < W && redo < 0; ++r) {
-                Unpacker u(c->xgot[r]);
-                u.get<int32_t>();
-                std::vector<int32_t> a, b2, se, c3;
-                u.get_vec(a);
-                const int32_t hasB = u.get<int32_t>();
-                u.get_vec(b2); u.get_vec(se);
-                const int32_t hasC = u.get<int32_t>();
-                const int32_t cc = u.get<int32_t>(), cp = u.get<int32_t>(), cl = u.get<int32_t>();
-                u.get_vec(c3);
-                if (!u.ok) return fail(c, SQ_E_ARG, "sharded run: malformed seed payload");
-                auto append = [&](const std::vector<int32_t>& v, size_t from) { for (size_t i = from; i + 2 < v.size(); i += 3) all.push_back(Node{v[i], v[i + 1], v[i + 2], 0, 0.0}); };
-                if (g.first_chr[r] < 0) continue;                      // no kept record: nothing replayed, nothing emitted
-                if (all.empty() || !hasB) { append(a, 0); continue; }  // nothing has been emitted before this shard
-                const Node& last = all.back();
-                bool exact_needed = last.chr >= g.first_chr[r];
-                for (int32_t v : se) if (v == last.pos + last.len) exact_needed = true;  // the one comparison without a chromosome test (:623)
-                if (!exact_needed) { append(b2, 0); continue; }
-                if (hasC && cc == last.chr && cp == last.pos && cl == last.len && c3.size() >= 3) {
-                    all.back() = Node{c3[0], c3[1], c3[2], 0, 0.0};  // the shard may have extended the node in front of it
-                    append(c3, 3);
-                    continue;
-                }
-                redo = r;
-                if (r == me) {
-                    HostClock hc(c, "host_segment_replay");
-                    g.seedC = last; g.hasC = true;
-                    rc = segment_replay(c, *g.plan, g.seedsC, false, nullptr, &g.seedC);
-                    if (rc) return rc;
-                }
-            }
-            if (redo >= 0) { pack_seeds(c, g); return need_exchange(c); }
-            g.seeds.swap(all);
-        }
-        {
-            HostClock hc(c, "host_tile_genome");
-            std::vector<Node> seedcopy = g.seeds;
-            rc = tile_genome(c, seedcopy, c->nodes);
-        }
-        if (rc) return rc;
-        rc = dev_upload_nodes(c, c->nodes);
-        if (rc) return rc;
-        // the chimeric edges are host work on the (small) fragment list: do them on a second thread while this one
-        // drives the depth and edge kernels over the concordant stream
-        c->edges.clear();
-        double chim_ms = 0;
-        // (sq_chimeric_on_device: RawEdgesChim as kernels on this stream, in front of the depth stage; a stage with more soft fragments than
-        // the bound comes back and takes the host route below)
-        c->chim_s1_device = false;
-        if (c->chim_dev_on()) {
-            bool fb = false;
-            c->timer.add("chim_device_fallback", 0, 0, 0);
-            rc = dev_chimeric_edges(c, g.raw, fb);
-            if (rc) return rc;
-            if (fb) c->timer.add("chim_device_fallback", 0, 0, 1); else c->chim_s1_device = true;
-        }
-        std::future<int> chim;
-        if (!c->chim_s1_device) chim = c->pool->submit([&]() {
-            const auto t0 = std::chrono::steady_clock::now();
-            const int r2 = chimeric_edges(c, g.raw);
-            chim_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            return r2;
-        });
-        std::vector<int32_t> unused;
-        rc = dev_node_depth(c, c->nodes, g.n_break, g.sup, g.sl, g.tiny_boundary, g.amb_plus, g.amb_minus, unused);
-        int rc_edges = rc ? rc : dev_concordant_edges(c, c->nodes, g.conc);
-        const int rc_chim = chim.valid() ? chim.get() : SQ_OK;
-        if (!c->chim_s1_device) c->timer.add("host_chimeric_edges", chim_ms);
-        if (rc_chim) return rc_chim;
-        if (rc_edges) return rc_edges;
-        g.stage = 4;
-        if (sh.on) {  // exchange 4 (the data exchange): per-node depth accumulators of the own chromosomes + locally reduced edges
-            const std::vector<Node>& N = c->nodes;
-            const int nn = (int)N.size();
-            int lo = 0, hi = 0;
-            while (lo < nn && N[lo].chr < sh.first_ref) ++lo;
-            hi = lo;
-            while (hi < nn && N[hi].chr < sh.end_ref) ++hi;
-            for (int i = 0; i < nn; ++i)
-                if ((i < lo || i >= hi) && (g.sup[i] || g.sup[nn + i] || g.sl[i] || g.sl[nn + i] || g.amb_plus[i] || g.amb_minus[i]))
-                    return fail(c, SQ_E_ARG, "internal: a record of this shard was counted for a node of another shard");
-            Packer pk(c->xbuf);
-            pk.put<int32_t>(X_GRAPH);
-            pk.put<int32_t>(lo); pk.put<int32_t>(hi);
-            pk.put<int64_t>((int64_t)g.sup[2 * nn]);  // |ReadsOther| of this shard
-            pk.put<int32_t>(g.tiny_boundary ? 1 : 0);
-            std::vector<int32_t> part;
-            auto slice = [&](auto&& get) { part.clear(); for (int i = lo; i < hi; ++i) part.push_back((int32_t)get(i)); pk.put_vec(part); };
-            slice([&](int i) { return g.sup[i]; }); slice([&](int i) { return g.sl[i]; }); slice([&](int i) { return g.sup[nn + i]; }); slice([&](int i) { return g.sl[nn + i]; });
-            slice([&](int i) { return g.amb_plus[i]; }); slice([&](int i) { return g.amb_minus[i]; });
-            std::vector<uint64_t> keys; std::vector<int32_t> ws;
-            for (const Edge& e : g.conc) { keys.push_back(edge_pack(e)); ws.push_back(e.w); }
-            pk.put_vec(keys); pk.put_vec(ws);
-            pk.put<int64_t>(c->counts.n_raw_edges);
-            return need_exchange(c);
-        }
-    }
-    if (g.stage != 4 && g.stage != 5) return fail(c, SQ_E_ARG, "internal: bad build stage");
-    std::vector<Node>& N = c->nodes;
-    const int nn = (int)N.size();
-    const bool resumed = g.stage == 5;  // back from the exchange of the ReadsOther lists (exact depth sweep of a sharded run)
-    if (sh.on && !resumed) {
-        rc = take_exchange(c, X_GRAPH);
-        if (rc) return rc;
-        g.sup.assign(2 * nn + 1, 0); g.sl.assign(2 * nn, 0); g.amb_plus.assign(nn, 0); g.amb_minus.assign(nn, 0);
-        g.tiny_boundary = false; g.conc.clear();
-        int64_t n_other = 0, n_raw = 0;
-        for (int r = 0; r < W; ++r) {
-            Unpacker u(c->xgot[r]);
-            u.get<int32_t>();
-            const int lo = u.get<int32_t>(), hi = u.get<int32_t>();
-            n_other += u.get<int64_t>();
-            if (u.get<int32_t>()) g.tiny_boundary = true;
-            std::vector<int32_t> v[6];
-            for (auto& x : v) u.get_vec(x);
-            std::vector<uint64_t> keys; std::vector<int32_t> ws;
-            u.get_vec(keys); u.get_vec(ws);
-            n_raw += u.get<int64_t>();
-            if (!u.ok || lo < 0 || hi > nn || lo > hi || keys.size() != ws.size()) return fail(c, SQ_E_ARG, "sharded run: malformed graph payload");
-            for (auto& x : v) if ((int)x.size() != hi - lo) return fail(c, SQ_E_ARG, "sharded run: malformed graph payload");
-            for (int i = lo; i < hi; ++i) {
-                g.sup[i] += v[0][i - lo]; g.sl[i] += v[1][i - lo]; g.sup[nn + i] += v[2][i - lo]; g.sl[nn + i] += v[3][i - lo];
-                g.amb_plus[i] += v[4][i - lo]; g.amb_minus[i] += v[5][i - lo];
-            }
-            for (size_t i = 0; i < keys.size(); ++i) {
-                Edge e;
-                e.a = (int32_t)(keys[i] >> 32); e.b = (int32_t)((keys[i] & 0xffffffffull) >> 2); e.ha = (keys[i] >> 1) & 1; e.hb = keys[i] & 1; e.w = ws[i]; e.gw = 0;
-                g.conc.push_back(e);
-            }
-        }
-        g.sup[2 * nn] = (int32_t)std::min<int64_t>(n_other, INT32_MAX);
-        c->counts.n_raw_edges = n_raw;
-    }
-    // per-node Support / AvgDepth (SegmentGraph.cpp:766-826): discordant blocks on the host, stream blocks from the GPU
-    std::vector<int32_t> dis_cnt(nn), dis_sum(nn);
-    {
-        HostClock hc(c, "host_depth_discordant");
-        const std::vector<Blk>& disc = g.disc;
-        size_t it = 0;
-        for (int i = 0; i < nn; ++i) {
-            int cnt = 0, sum = 0;
-            for (; it != disc.size() && disc[it].refid == N[i].chr && disc[it].refpos < N[i].pos + N[i].len; ++it)
-                if (disc[it].refpos >= N[i].pos && disc[it].refpos + disc[it].matchref <= N[i].pos + N[i].len) { ++cnt; sum += disc[it].matchref; }
-            dis_cnt[i] = cnt; dis_sum[i] = sum;
-        }
-    }
-    // ReadsOther (non-first blocks) is sorted with an unstable std::sort in the reference (SegmentGraph.cpp:781) and a
-    // block of <= 3 bases right behind a node boundary is counted for whichever node the sweep cursor is on, which
-    // depends on that sort's tie order.  Node depths only feed the coverage-ratio test of FilterEdges, so by default
-    // the GPU reports canonical depths plus bounds over all tie orders and FilterEdges checks that no decision can
-    // change inside the bounds; only then (or when SQUID_EXACT_DEPTH is set, as the stage-parity tests do) is the
-    // reference's sort repeated on the host and the sweep walked exactly.  A sharded run cannot repeat that sort (its
-    // tie order depends on the whole list) and fails loudly instead.
-    const bool exact_mode = env_set("SQUID_EXACT_DEPTH") && !sh.on;
-    struct OtherR { int32_t chr, pos, len; };
-    std::vector<OtherR> other_sorted;
-    auto sort_other = [&]() { std::sort(other_sorted.begin(), other_sorted.end(), [](const OtherR& a, const OtherR& b) { return a.chr != b.chr ? a.chr < b.chr : a.pos < b.pos; }); };
-    auto exact_sort = [&](bool always) -> int {  // always: fetch the list even when no block sits in a corner (the forced retry of the tests)
-        std::vector<int32_t> ochr, opos, olen;
-        bool has_tiny = false;
-        int r2 = dev_gather_other(c, g.n_break, has_tiny, ochr, opos, olen, always);
-        if (r2) return r2;
-        other_sorted.resize(has_tiny || always ? ochr.size() : 0);
-        for (size_t i = 0; i < other_sorted.size(); ++i) other_sorted[i] = OtherR{ochr[i], opos[i], olen[i]};
-        sort_other();
-        return SQ_OK;
-    };
-    // combine in the reference's order: discordant, ReadsMain, ReadsOther, then the division (only when ReadsOther is
-    // non-empty, ledger B13).  `other` = per-node (count, sum) of ReadsOther, either canonical or from the exact sweep.
-    auto set_depths = [&](const std::vector<int32_t>& ocnt, const std::vector<int32_t>& osum, bool bounds) {
-        const int64_t n_other = g.sup[2 * nn];
-        c->depth_bounds = bounds;
-        for (int i = 0; i < nn; ++i) {
-            N[i].support = dis_cnt[i] + g.sup[i];
-            double d = dis_sum[i];
-            d += (int32_t)g.sl[i];
-            double lo = d, hi = d;
-            if (n_other != 0) {
-                N[i].support += ocnt[i];
-                d += osum[i];
-                lo = d; hi = d;
-                if (bounds) { lo = d - g.amb_minus[i]; hi = d + g.amb_plus[i]; }
-                d = 1.0 * d / N[i].len; lo = 1.0 * lo / N[i].len; hi = 1.0 * hi / N[i].len;
-            }
-            N[i].depth = d; N[i].depth_lo = lo; N[i].depth_hi = hi;
-        }
-    };
-    auto exact_sweep = [&](std::vector<int32_t>& ocnt, std::vector<int32_t>& osum) {
-        ocnt.assign(nn, 0); osum.assign(nn, 0);
-        size_t it = 0;
-        for (int i = 0; i < nn; ++i)
-            for (; it != other_sorted.size(); ++it) {
-                const OtherR& r = other_sorted[it];
-                if (r.chr == N[i].chr && r.pos >= N[i].pos - 3 && r.pos + r.len <= N[i].pos + N[i].len + 3) { ocnt[i]++; osum[i] += r.len; }
-                else if (r.pos >= N[i].pos + N[i].len || r.chr != N[i].chr) break;
-            }
-    };
-    std::vector<int32_t> ocnt(nn), osum(nn);
-    for (int i = 0; i < nn; ++i) { ocnt[i] = g.sup[nn + i]; osum[i] = (int32_t)g.sl[nn + i]; }
-    c->depth_ambiguous = false;
-    if (exact_mode && g.tiny_boundary) {
-        HostClock hc(c, "host_depth_exact_sweep");
-        rc = exact_sort(false);
-        if (rc) return rc;
-        if (!other_sorted.empty()) exact_sweep(ocnt, osum);
-        set_depths(ocnt, osum, false);
-    } else set_depths(ocnt, osum, g.tiny_boundary);
-    const bool host_filters = host_filters_env();
-    if (!resumed) {
-        if (c->keep_stages) c->snap[1].take(c->nodes, c->edges, nullptr);
-        {
-            HostClock hc(c, "host_edge_reduce");
-            g.raw.insert(g.raw.end(), g.conc.begin(), g.conc.end());
-            reduce_edges(g.raw, c->edges, c->pool ? std::min(c->pool->size() + 1, 32) : 1);
-        }
-        if (c->keep_stages) c->snap[2].take(c->nodes, c->edges, nullptr);
-    }
-    // K6 / K7 run on the device (sq_graph_kernels.inc); SQUID_HOST_FILTERS=1 takes the host restatements of sq_graph.cpp instead
-    // (kept as a cross-check: tests compare the two stage by stage)
-    {
-        HostClock hc(c, host_filters ? "host_filters" : "wall_filters");
-        if (!resumed) {
-            if (host_filters) filter_by_weight(c); else if ((rc = dev_filter_by_weight(c))) return rc;
-            if (c->keep_stages) c->snap[3].take(c->nodes, c->edges, nullptr);
-            if (host_filters) filter_by_interleaving(c, g.keep); else if ((rc = dev_filter_by_interleaving(c, g.keep))) return rc;
-            g.before = c->edges;
-            if (host_filters) filter_edges(c, g.keep); else if ((rc = dev_filter_edges(c, g.keep))) return rc;
-            if (env_set("SQUID_FORCE_DEPTH_RETRY")) c->depth_ambiguous = true;  // (tests: take the exact sweep whatever the bounds say)
-        }
-        if (c->depth_ambiguous || resumed) {
-            // some coverage-ratio decision depends on the tie order: repeat the reference's sort and sweep, then redo the
-            // filter with the exact depths.  A sharded run needs every shard's ReadsOther for that (the tie order of the unstable
-            // sort depends on the whole list): one more exchange -- the lists, in rank order, are the unsharded stream order
-            HostClock hc2(c, "host_depth_exact_retry");
-            if (sh.on && !resumed) {
-                std::vector<int32_t> ochr, opos, olen;
-                bool has_tiny = false;
-                rc = dev_gather_other(c, g.n_break, has_tiny, ochr, opos, olen, true);
-                if (rc) return rc;
-                Packer pk(c->xbuf);
-                pk.put<int32_t>(X_OTHER);
-                pk.put_vec(ochr); pk.put_vec(opos); pk.put_vec(olen);
-                g.stage = 5;
-                return need_exchange(c);
-            }
-            if (sh.on) {
-                rc = take_exchange(c, X_OTHER);
-                if (rc) return rc;
-                other_sorted.clear();
-                for (int r = 0; r < W; ++r) {
-                    Unpacker u(c->xgot[r]);
-                    u.get<int32_t>();
-                    std::vector<int32_t> a, b, d;
-                    u.get_vec(a); u.get_vec(b); u.get_vec(d);
-                    if (!u.ok || a.size() != b.size() || a.size() != d.size()) return fail(c, SQ_E_ARG, "sharded run: malformed ReadsOther payload");
-                    for (size_t i = 0; i < a.size(); ++i) other_sorted.push_back(OtherR{a[i], b[i], d[i]});
-                }
-                sort_other();
-            } else {
-                rc = exact_sort(true);  // (with nothing fetched the sweep below would zero every ReadsOther contribution)
-                if (rc) return rc;
-            }
-            exact_sweep(ocnt, osum);
-            set_depths(ocnt, osum, false);
-            c->depth_ambiguous = false;
-            c->edges = g.before;
-            if (host_filters) filter_edges(c, g.keep); else if ((rc = dev_filter_edges(c, g.keep))) return rc;
-        }
-        if (c->keep_stages) c->snap[4].take(c->nodes, c->edges, nullptr);
-    }
-    return finish_graph(c, host_filters);
-}
-
-struct SvBuild {
-    int stage = 0;
-    BPMap bpmap;
-    // the breakpoint pairs of every edge, once (edge i: entries [eoff[i], eoff[i + 1]); round 4 looked every edge up three times in the map)
-    std::vector<int32_t> eoff;
-    std::vector<std::pair<std::pair<int, int>, std::pair<int, int>>> ebp;
-    std::vector<uint8_t> eexact;
-    std::vector<std::pair<int, int>> BPs;
-    std::vector<int32_t> diff;  // this shard's difference array
-    int cur_prev = 0;
-    BpBoundary bb;
-};
-
-static int call_sv(sq_ctx* c) {
-    HostClock wall(c, "wall_call_sv");
-    if (!c->ordered) return fail(c, SQ_E_ARG, "sq_call_sv before sq_order");
-    const std::vector<Node>& N = c->nodes;
-    std::vector<Edge>& E = c->edges;
-    Shard& sh = c->shard;
-    if (!c->svb) c->svb = std::make_shared<SvBuild>();
-    SvBuild& v = *c->svb;
-    BPMap& bpmap = v.bpmap;
-    // breakpoint list of every edge (SegmentGraph.cpp:3091-3109): the pairs ExactBreakpoint found, else the node ends the edge touches
-    const size_t m = E.size();
-    auto par = [&](size_t n, const std::function<void(size_t, size_t)>& f) {  // [lo, hi) pieces on the context's host threads
-        const int np = (c->pool && n > 20000) ? 4 * (c->pool->size() + 1) : 1;
-        if (np <= 1) { f(0, n); return; }
-        c->pool->parallel_for(np, 1 << 20, [&](int k) { f(n * (size_t)k / (size_t)np, n * ((size_t)k + 1) / (size_t)np); });
-    };
-    auto build_edge_table = [&]() {
-        v.eoff.assign(m + 1, 0); v.eexact.assign(m, 0);
-        std::vector<const std::vector<std::pair<int, int>>*> hit(m, nullptr);
-        par(m, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; ++i) {
-                BPMap::const_iterator it = bpmap.find(edge_pack(E[i]));
-                if (it != bpmap.end() && !it->second.empty()) { hit[i] = &it->second; v.eexact[i] = 1; v.eoff[i + 1] = (int32_t)it->second.size(); }
-                else v.eoff[i + 1] = 1;
-            }
-        });
-        for (size_t i = 0; i < m; ++i) v.eoff[i + 1] += v.eoff[i];
-        v.ebp.resize((size_t)v.eoff[m]);
-        par(m, [&](size_t lo, size_t hi) {
-            for (size_t i = lo; i < hi; ++i) {
-                const Edge& e = E[i];
-                size_t o = (size_t)v.eoff[i];
-                if (hit[i]) for (const auto& p : *hit[i]) v.ebp[o++] = {{N[e.a].chr, p.first}, {N[e.b].chr, p.second}};
-                else v.ebp[o] = {{N[e.a].chr, e.ha ? N[e.a].pos : N[e.a].pos + N[e.a].len}, {N[e.b].chr, e.hb ? N[e.b].pos : N[e.b].pos + N[e.b].len}};
-            }
-        });
-    };
-    std::vector<std::pair<int, int>>& BPs = v.BPs;
-    std::vector<int32_t> cov;
-    int rc;
-    auto pack_bpsup = [&]() {
-        Packer pk(c->xbuf);
-        pk.put<int32_t>(X_BPSUP);
-        pk.put<int32_t>(v.cur_prev); pk.put<int32_t>(v.bb.cur_end); pk.put<int32_t>(v.bb.has_p3 ? 1 : 0); pk.put<int32_t>(v.bb.has_event ? 1 : 0);
-        pk.put<int64_t>(v.bb.n_p3); pk.put<int64_t>(v.bb.absorb);
-        pk.put_vec(v.diff);
-    };
-    if (v.stage == 0) {
-        if (c->chim_s2_pending || c->chim_s1_device) {  // (chim_s1_device without a pending stage: a second sq_call_sv on the same graph)
-            if (!c->chim_s2_pending) { bool fb = false; rc = dev_exact_breakpoints_start(c, fb); if (rc) return rc; if (fb) return fail(c, SQ_E_ARG, "internal: the breakpoint stage of this graph ran on the device before and does not now"); }
-            c->chim_s2_pending = false;
-            rc = dev_exact_breakpoints_collect(c, bpmap);
-            if (rc) return rc;
-        } else if (c->bp_future.valid()) {
-            rc = c->bp_future.get();
-            c->timer.add("host_exact_breakpoints", c->bp_early_ms);
-            if (rc) return rc;
-            bpmap.swap(*c->bp_early);
-            c->bp_early.reset();
-        } else {
-            HostClock hc(c, "host_exact_breakpoints");
-            rc = exact_breakpoints(c, bpmap);
-            if (rc) return rc;
-        }
-        build_edge_table();
-        BPs.resize(2 * v.ebp.size());
-        par(v.ebp.size(), [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; ++k) { BPs[2 * k] = v.ebp[k].first; BPs[2 * k + 1] = v.ebp[k].second; } });
-        // (equal elements are indistinguishable pairs: any sort gives the reference's sorted list; the threaded introsort of sq_parsort.h)
-        std_sort_parallel(BPs.begin(), BPs.end(), std::less<std::pair<int, int>>(), c->pool ? std::min(c->pool->size() + 1, 32) : 1, true);
-        static const bool bp_host = env_set("SQUID_BP_HOST");  // debug cross-check of k_bp_walk
-        if (c->bwa) {  // (--bwa: the records and their names are on the host; sq_bwa_on_device: the records are in HBM as well)
-            rc = c->bwa_dev_active ? bwa_breakpoint_support_device(c, BPs, cov) : bwa_breakpoint_support(c, BPs, cov);
-            if (rc) return rc;
-        } else if (!sh.on) {
-            rc = bp_host ? dev_breakpoint_support_exact(c, BPs, cov) : dev_breakpoint_support(c, BPs, cov);
-            if (rc) return rc;
-        } else {
-            // the cursor (SegmentGraph.cpp:3157) is carried from shard to shard: start from the usual state -- every
-            // breakpoint on an earlier chromosome is behind it -- and let the exchange verify that guess
-            v.cur_prev = (int)(std::lower_bound(BPs.begin(), BPs.end(), std::make_pair(sh.first_ref, INT32_MIN)) - BPs.begin());
-            rc = dev_breakpoint_support(c, BPs, v.diff, v.cur_prev, &v.bb, true);
-            if (rc) return rc;
-            pack_bpsup();
-            v.stage = 1;
-            return need_exchange(c);
-        }
-    } else {
-        rc = take_exchange(c, X_BPSUP);
-        if (rc) return rc;
-        const int W = c->P.world_size, me = c->P.rank;
-        const size_t nb = BPs.size();
-        std::vector<int64_t> total(nb + 1, 0);
-        int truth = 0, bad = -1;
-        for (int r = 0; r < W; ++r) {
-            Unpacker u(c->xgot[r]);
-            u.get<int32_t>();
-            const int assumed = u.get<int32_t>(), end = u.get<int32_t>(), has = u.get<int32_t>(), has_event = u.get<int32_t>();
-            const int64_t n_p3 = u.get<int64_t>(), absorb = u.get<int64_t>();
-            std::vector<int32_t> d;
-            u.get_vec(d);
-            if (!u.ok || d.size() != nb + 1) return fail(c, SQ_E_ARG, "sharded run: malformed breakpoint payload");
-            if (!has) continue;  // no pass-3 record: the cursor passes through untouched
-            // a cursor that arrives `lag` entries behind the assumed position catches up one entry per pass-3 record;
-            // every breakpoint it still has to pass lies on an earlier chromosome, so nothing counted here changes as
-            // long as it has caught up before the first record that moves it further
-            const int64_t lag = (int64_t)assumed - truth;
-            if (lag < 0 || lag > absorb) { bad = r; break; }
-            truth = has_event ? end : (int)std::min<int64_t>(assumed, (int64_t)truth + n_p3);
-            for (size_t i = 0; i <= nb; ++i) total[i] += d[i];
-        }
-        if (bad >= 0) {
-            // rank `bad` started from a wrong cursor (an earlier shard ended while the cursor was still catching up): it
-            // recounts from the real one, everybody exchanges again
-            if (bad == me) {
-                v.cur_prev = truth;
-                rc = dev_breakpoint_support(c, BPs, v.diff, v.cur_prev, &v.bb, true);
-                if (rc) return rc;
-            }
-            pack_bpsup();
-            return need_exchange(c);
-        }
-        cov.assign(nb, 0);
-        int64_t run = 0;
-        for (size_t i = 0; i < nb; ++i) { run += total[i]; cov[i] = (int32_t)run; }
-    }
-    // per-edge table in key order (parity tests) -- before the weight sort
-    const size_t nbp = v.ebp.size();
-    std::vector<int32_t> sup1(nbp), sup2(nbp);
-    par(nbp, [&](size_t lo, size_t hi) {
-        for (size_t k = lo; k < hi; ++k) {
-            sup1[k] = cov[(size_t)(std::lower_bound(BPs.begin(), BPs.end(), v.ebp[k].first) - BPs.begin())];
-            sup2[k] = cov[(size_t)(std::lower_bound(BPs.begin(), BPs.end(), v.ebp[k].second) - BPs.begin())];
-        }
-    });
-    c->bp_off.assign(v.eoff.begin(), v.eoff.end());
-    c->bp1.resize(nbp); c->bp2.resize(nbp);
-    c->bsup1 = sup1; c->bsup2 = sup2;
-    par(m, [&](size_t lo, size_t hi) {
-        for (size_t i = lo; i < hi; ++i)
-            for (int32_t k = v.eoff[i]; k < v.eoff[i + 1]; ++k) { c->bp1[(size_t)k] = v.eexact[i] ? v.ebp[(size_t)k].first.second : -1; c->bp2[(size_t)k] = v.eexact[i] ? v.ebp[(size_t)k].second.second : -1; }
-    });
-    multiply_discordant(c, true);
-    // WriteBEDPE (src/WriteIO.cpp:45-124): unstable sort by weight on the key-sorted edge list (ledger B8).  What is sorted is the index of
-    // every edge with the reference's comparison on the weights: libstdc++'s introsort takes the same decisions, hence the same order
-    HostClock hc(c, "host_select_sv");
-    std::vector<int32_t> W(m);
-    for (size_t i = 0; i < m; ++i) W[i] = (int32_t)i;
-    std::sort(W.begin(), W.end(), [&](int32_t a, int32_t b) { return E[(size_t)a].w > E[(size_t)b].w; });
-    // rank / sign of every node in its component order
-    std::vector<int> comp(N.size(), -1), rank(N.size(), -1), sign(N.size(), 1);
-    par(c->ord_off.size() - 1, [&](size_t lo, size_t hi) {
-        for (size_t k = lo; k < hi; ++k)
-            for (int j = c->ord_off[k]; j < c->ord_off[k + 1]; ++j) {
-                int nd = std::abs(c->ord_nodes[j]) - 1;
-                comp[nd] = (int)k; rank[nd] = j - c->ord_off[k]; sign[nd] = c->ord_nodes[j] < 0 ? -1 : 1;
-            }
-    });
-    for (auto& col : c->sv_cols) col.clear();
-    c->sv_s1.clear(); c->sv_s2.clear();
-    for (const int32_t wi : W) {
-        const Edge& e = E[(size_t)wi];
-        const Node &a = N[e.a], &b = N[e.b];
-        bool conc = a.chr == b.chr && e.ha == 0 && e.hb == 1 && (b.pos - a.pos - a.len <= c->P.concord_dist_pos || e.b - e.a <= c->P.concord_dist_idx);
-        if (conc) continue;
-        bool ok = false;
-        if (comp[e.a] == comp[e.b] && rank[e.a] < rank[e.b] && (bool)e.ha == (sign[e.a] < 0) && (bool)e.hb == (sign[e.b] > 0)) ok = true;
-        else if (comp[e.a] == comp[e.b] && rank[e.a] > rank[e.b] && (bool)e.hb == (sign[e.b] < 0) && (bool)e.ha == (sign[e.a] > 0)) ok = true;
-        if (!ok) continue;
-        for (int32_t k = v.eoff[(size_t)wi]; k < v.eoff[(size_t)wi + 1]; ++k) {
-            int b1 = v.ebp[(size_t)k].first.second, b2 = v.ebp[(size_t)k].second.second;
-            c->sv_cols[0].push_back(a.chr); c->sv_cols[1].push_back(e.ha ? b1 : a.pos); c->sv_cols[2].push_back(e.ha ? a.pos + a.len : b1);
-            c->sv_cols[3].push_back(b.chr); c->sv_cols[4].push_back(e.hb ? b2 : b.pos); c->sv_cols[5].push_back(e.hb ? b.pos + b.len : b2);
-            c->sv_cols[6].push_back(e.w); c->sv_cols[7].push_back(sup1[(size_t)k]); c->sv_cols[8].push_back(sup2[(size_t)k]);
-            c->sv_s1.push_back(e.ha); c->sv_s2.push_back(e.hb);
-        }
-    }
-    c->svb.reset();
-    return SQ_OK;
-}
 
 }  // namespace sq
 

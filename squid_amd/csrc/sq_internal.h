@@ -236,7 +236,8 @@ struct HostBatch;      // decoded records on the host (below)
 
 // Chromosome sharding: rank r holds the concordant records of a contiguous RefID range and
 // everything that is small (chimeric fragments, cluster table, node and edge tables) is replicated.  The fields
-// below are what a rank learns about the other shards from the exchanges (see build_graph in sq_capi.cpp).
+// below are what a rank learns about the other shards from the exchanges (the payloads and the decisions taken from them: sq_shard.h;
+// the stages of build_graph that exchange them: sq_build.cpp).
 struct Shard {
     bool on = false;
     int first_ref = 0, end_ref = 0;   // owns RefIDs [first_ref, end_ref); the last rank also owns RefID -1
@@ -248,7 +249,7 @@ struct Shard {
     long long other_seed = INT64_MIN; // running (otherChr << 32 | otherrightmost) of the earlier ranks
     int64_t n_break_global = 0;
 };
-struct GraphBuild;  // locals of sq_build_graph that survive an exchange (sq_capi.cpp)
+struct GraphBuild;  // locals of sq_build_graph that survive an exchange (sq_shard.h)
 struct SegPlan;     // sq_segment.cpp
 struct RcclTransport;  // sq_exchange.cpp
 void exchange_release(sq_ctx* c);
@@ -639,5 +640,11 @@ struct BpBoundary {  // what the next shard needs to know about the breakpoint c
 };
 int dev_breakpoint_support(sq_ctx* c, const std::vector<std::pair<int, int>>& bps_sorted, std::vector<int32_t>& coverage, int cur_prev = 0, BpBoundary* bb = nullptr,
                            bool raw_diff = false);
+int dev_breakpoint_support_exact(sq_ctx* c, const std::vector<std::pair<int, int>>& bps, std::vector<int32_t>& coverage);  // SQUID_BP_HOST: debug cross-check of k_bp_walk
+
+// ---- sq_build.cpp (the pipelines behind sq_build_graph / sq_call_sv; each returns SQ_NEED_EXCHANGE when a sharded run has packed a payload)
+int build_graph(sq_ctx* c);
+int build_graph_bwa(sq_ctx* c);
+int call_sv(sq_ctx* c);
 
 }  // namespace sq
