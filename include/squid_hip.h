@@ -219,6 +219,18 @@ int sq_bwa_nodes_on_device(sq_ctx* c, int32_t on);
  * run again on the host, the records of the longest; k_seg_run, host_segment_walk; host_segment_replay is absent when the route was taken). */
 int sq_segment_on_device(sq_ctx* c, int32_t on);
 
+/* on != 0: the device version of FurtherCompressNode (src/SegmentGraph.cpp:2693-2892) walks the node list with one wave per independent window
+ * instead of one wave per chromosome (squid_amd/csrc/sq_compress_stage.inc).  A node i behind its chromosome's first node starts a window when
+ * no concordant edge of a node behind the last discordant node p in front of it reaches i or further, and p and the first discordant node q at
+ * or behind i are not fewer than 20 nodes apart; the walk arrives there in the state of a chromosome start, so the wave's ids only need the
+ * number of ids in front of it.  Every result is identical to the per-chromosome route's.  Default: off.  The stage is the
+ * same code everywhere, so the switch applies to STAR contexts, --bwa contexts, chromosome-sharded contexts (sq_set_shard) and route 1 of
+ * sq_debug_graph_stages alike.  SQUID_COMPRESS_WINDOWS_GPU=1 / =0 in the environment of sq_create forces / forbids the route whatever this call
+ * says.  A node whose discordant edge list outgrows the kernel's capacity hands the whole graph to the host function, as on the default route
+ * (sq_get_timing: k_fc_cuts, inside k_further_compress; fc_windows, fc_longest_window: the windows walked and the nodes of the longest, absent
+ * when the route was not taken). */
+int sq_compress_windows_on_device(sq_ctx* c, int32_t on);
+
 /* vector<vector<int>> Ordering() -- src/SegmentGraph.cpp:3236-3262: CSR of signed 1-based node ids */
 typedef struct sq_orders {
     int32_t n_components;
@@ -387,6 +399,11 @@ typedef struct sq_graph_stages_debug {
 } sq_graph_stages_debug;
 int sq_debug_graph_stages(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, const double* depth3, int32_t n_edges, const int32_t* edges6, const uint8_t* keep_in, int32_t bounds,
                           int32_t route, int32_t first, int32_t last, const sq_params* params, sq_graph_stages_debug* out);
+/* tests: the window table of sq_compress_windows_on_device alone.  One caller-supplied graph as it ENTERS FurtherCompressNode (nodes4, edges6 as
+ * for sq_debug_graph_stages; params: concord_dist_pos / concord_dist_idx for this call, NULL: the context's) goes through the context's upload,
+ * the incidence lists, the per-node summary and the cut kernels, whatever the switch says.  windows[0 .. n_windows]: the first node of every
+ * window, windows[n_windows] = n_nodes; valid until the next call on this thread.  Uses up the context's graph. */
+int sq_debug_fc_windows(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, int32_t n_edges, const int32_t* edges6, const sq_params* params, int32_t* n_windows, const int32_t** windows);
 /* tests: the node depth loop of BuildNode_BWA (src/SegmentGraph.cpp:1180-1200) on caller-supplied tables.  nodes3: n_nodes x {chr, pos, len},
  * sorted, the nodes of a chromosome not overlapping; reads3: n_reads x {RefID, RefPos, MatchRef}, the Reads list in its order.  route 0: the host
  * loop (needs no device: c may be null); route 1: the kernels of sq_bwa_on_device.  support / sums: per node the count and the 32-bit sum of

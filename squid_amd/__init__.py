@@ -29,6 +29,7 @@ EXPORTS = [
     "sq_bwa_edges_on_device", "sq_debug_bwa_raw_edges", "sq_debug_bwa_raw_edges_tables",
     "sq_bwa_nodes_on_device", "sq_debug_bwa_seed_nodes", "sq_debug_bwa_seed_nodes_tables",
     "sq_segment_on_device", "sq_debug_segment_seeds", "sq_debug_segment_seeds_tables",
+    "sq_compress_windows_on_device", "sq_debug_fc_windows",
 ]
 
 
@@ -142,6 +143,8 @@ def load_library() -> C.CDLL:
         lib.sq_debug_bwa_seed_nodes.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqBwaNodesDebug)]
         lib.sq_debug_bwa_seed_nodes_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _P32, C.POINTER(C.c_uint32), _P32, C.POINTER(SqBwaNodesDebug)]
         lib.sq_segment_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_compress_windows_on_device.argtypes = [C.c_void_p, C.c_int32]
+        lib.sq_debug_fc_windows.argtypes = [C.c_void_p, C.c_int32, _P32, C.c_int32, _P32, C.POINTER(SqParams), C.POINTER(C.c_int32), C.POINTER(_P32)]
         lib.sq_debug_segment_seeds.argtypes = [C.c_void_p, C.c_int32, C.POINTER(SqSegmentDebug)]
         lib.sq_debug_segment_seeds_tables.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, _P32, C.c_int32, _P32, C.c_int32, _P32, C.c_int32, _P32, _P32, _P32, _P32, C.c_int32, _P32,
                                                       C.POINTER(SqSegmentDebug)]
@@ -459,6 +462,37 @@ class Context:
         self._chk(self.lib.sq_debug_graph_stages(self.h, n, ip(ni), C.cast(nd.buffer_info()[0], C.POINTER(C.c_double)), m, ip(ei), kb, 1 if bounds else 0, route, first, last,
                                                  C.byref(p) if p is not None else None, C.byref(out)), "sq_debug_graph_stages")
         return {"keep": bytes(C.string_at(out.keep, out.n_keep)) if out.n_keep else b"", "depth_ambiguous": int(out.depth_ambiguous), "fallback": int(out.fallback), "rc": int(out.rc)}
+
+    def compress_windows_on_device(self, on: bool = True):
+        """sq_compress_windows_on_device: the device version of FurtherCompressNode walks one wave per independent window of the node list instead of
+        one per chromosome (same results; STAR, --bwa and sharded contexts and route 1 of debug_graph_stages alike; off unless asked)"""
+        self._chk(self.lib.sq_compress_windows_on_device(self.h, 1 if on else 0), "sq_compress_windows_on_device")
+
+    def debug_fc_windows(self, nodes, edges, **params) -> list:
+        """sq_debug_fc_windows (tests): the window table of compress_windows_on_device for one graph as it enters FurtherCompressNode (nodes, edges as for
+        debug_graph_stages; params: concord_dist_pos, concord_dist_idx for this call): the first node of every window, then the node count.
+        Uses up the context's graph."""
+        import array
+
+        import numpy as np
+
+        ni, ei = array.array("i"), array.array("i")
+        for v in nodes:
+            ni.extend(v[:4])
+        for e in edges:
+            ei.extend(e[:5])
+            ei.append(e[5] if len(e) > 5 else 0)
+        ip = lambda a: C.cast(a.buffer_info()[0], _P32) if len(a) else None
+        p = None
+        if params:
+            p = SqParams.from_buffer_copy(self.params)
+            for k, v in params.items():
+                if k not in ("concord_dist_pos", "concord_dist_idx"):
+                    raise TypeError(f"debug_fc_windows: {k} is not a parameter the window table reads")
+                setattr(p, k, v)
+        nw, tab = C.c_int32(0), _P32()
+        self._chk(self.lib.sq_debug_fc_windows(self.h, len(nodes), ip(ni), len(edges), ip(ei), C.byref(p) if p is not None else None, C.byref(nw), C.byref(tab)), "sq_debug_fc_windows")
+        return np.ctypeslib.as_array(tab, shape=(nw.value + 1,)).tolist()
 
     def release_reader_buffers(self):
         """give back the device / page-locked memory the GPU reader keeps between ingests (sq_release_reader_buffers)"""

@@ -119,6 +119,7 @@ int sq_create(const sq_params* p, sq_ctx** out) {
     if (env_set("SQUID_BWA_EDGES_GPU")) c->bwa_edges_env = env_nonzero("SQUID_BWA_EDGES_GPU") ? 1 : 0;    // the same for the BAM loop of RawEdges of a --bwa context
     if (env_set("SQUID_SEGMENT_GPU")) c->seg_dev_env = env_nonzero("SQUID_SEGMENT_GPU") ? 1 : 0;          // the same for BuildNode_STAR's segmentation automaton (not --bwa, not sharded)
     if (env_set("SQUID_BWA_NODES_GPU")) c->bwa_nodes_env = env_nonzero("SQUID_BWA_NODES_GPU") ? 1 : 0;    // the same for the record automaton of BuildNode_BWA of a --bwa context
+    if (env_set("SQUID_COMPRESS_WINDOWS_GPU")) c->fc_windows_env = env_nonzero("SQUID_COMPRESS_WINDOWS_GPU") ? 1 : 0;  // the same for FurtherCompressNode's walk over windows (every context)
     int rc = dev_create(c);
     if (rc) { std::fprintf(stderr, "libsquid_hip: %s\n", c->err.c_str()); dev_destroy(c); delete c; return rc; }
     *out = c;
@@ -803,6 +804,11 @@ int sq_segment_on_device(sq_ctx* c, int32_t on) {
     c->seg_dev_asked = on != 0;  // (a --bwa context and a sharded one keep their host routes: seg_dev_on)
     return SQ_OK;
 }
+int sq_compress_windows_on_device(sq_ctx* c, int32_t on) {
+    if (!c) return SQ_E_ARG;
+    c->fc_windows_asked = on != 0;  // (every context looks at it: fc_windows_on)
+    return SQ_OK;
+}
 static int segment_debug_view(sq_ctx* c, SegPlan& plan, int read_len, int32_t route, sq_segment_debug* out) {
     static thread_local SegSeedsDebug R;
     std::memset(out, 0, sizeof *out);
@@ -1132,6 +1138,42 @@ static int sq_debug_graph_stages_impl(sq_ctx* c, int32_t n_nodes, const int32_t*
 int sq_debug_graph_stages(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, const double* depth3, int32_t n_edges, const int32_t* edges6, const uint8_t* keep_in, int32_t bounds,
                           int32_t route, int32_t first, int32_t last, const sq_params* params, sq_graph_stages_debug* out) {
     return abi_guard(c, "sq_debug_graph_stages", [&]() { return sq_debug_graph_stages_impl(c, n_nodes, nodes4, depth3, n_edges, edges6, keep_in, bounds, route, first, last, params, out); });
+}
+// (tests) the window table of sq_compress_windows_on_device for one caller-supplied graph as it enters FurtherCompressNode
+static int sq_debug_fc_windows_impl(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, int32_t n_edges, const int32_t* edges6, const sq_params* params, int32_t* n_windows, const int32_t** windows) {
+    if (!c || n_nodes <= 0 || n_edges < 0 || !nodes4 || (n_edges && !edges6) || !n_windows || !windows) return SQ_E_ARG;
+    if (c->bp_future.valid()) (void)c->bp_future.get();
+    dev_chim_drop_pending(c);
+    c->chim_s2_pending = false; c->chim_s1_device = false; c->graph_built = false; c->ordered = false; c->stage_view = false;
+    c->gb.reset();
+    std::vector<Node> N((size_t)n_nodes);
+    for (int32_t i = 0; i < n_nodes; ++i) {
+        const int32_t* v = nodes4 + 4 * (size_t)i;
+        if (v[2] <= 0 || (i > 0 && (v[0] < nodes4[4 * (size_t)(i - 1)]))) return fail(c, SQ_E_ARG, "sq_debug_fc_windows: node table is not sorted, or holds an empty node");
+        N[(size_t)i] = Node{v[0], v[1], v[2], v[3], 0.0, 0.0, 0.0};
+    }
+    std::vector<Edge> E((size_t)n_edges);
+    for (int32_t i = 0; i < n_edges; ++i) {
+        const int32_t* e = edges6 + 6 * (size_t)i;
+        if (e[0] < 0 || e[2] < e[0] || e[2] >= n_nodes) return fail(c, SQ_E_ARG, "sq_debug_fc_windows: edge outside the node table");
+        Edge& x = E[(size_t)i];
+        x.a = e[0]; x.ha = e[1] != 0; x.b = e[2]; x.hb = e[3] != 0; x.w = e[4]; x.gw = e[5];
+        if (i > 0 && edge_key_less(x, E[(size_t)i - 1])) return fail(c, SQ_E_ARG, "sq_debug_fc_windows: edges are not sorted by key");
+    }
+    c->nodes.swap(N); c->edges.swap(E); c->label.clear();
+    const sq_params saved = c->P;
+    if (params) { c->P.concord_dist_pos = params->concord_dist_pos; c->P.concord_dist_idx = params->concord_dist_idx; }  // (what IsDiscordant reads, for this call only)
+    static thread_local std::vector<int32_t> table;
+    const int rc = dev_fc_windows_debug(c, table);
+    dev_flush_timers(c);
+    c->P = saved;
+    c->nodes.clear(); c->edges.clear();
+    if (rc) return rc;
+    *n_windows = (int32_t)table.size() - 1; *windows = table.data();
+    return SQ_OK;
+}
+int sq_debug_fc_windows(sq_ctx* c, int32_t n_nodes, const int32_t* nodes4, int32_t n_edges, const int32_t* edges6, const sq_params* params, int32_t* n_windows, const int32_t** windows) {
+    return abi_guard(c, "sq_debug_fc_windows", [&]() { return sq_debug_fc_windows_impl(c, n_nodes, nodes4, n_edges, edges6, params, n_windows, windows); });
 }
 int sq_debug_order(sq_ctx* c, int32_t n, int32_t n_edges, const int32_t* edges5, int32_t use_gpu, int32_t* mask, int32_t* order, int64_t* value) {
     if (!c || n_edges < 0 || (n_edges && !edges5) || !mask || !order || !value) return SQ_E_ARG;

@@ -673,6 +673,28 @@ __global__ void k_fc_addoff(int n, int nseg, const int32_t* seg, const int32_t* 
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg[mid] <= i) lo = mid; else hi = mid; }
     merge[i] += segoff[lo];
 }
+// ---- the same walk cut at independent windows (sq_compress_windows_on_device; the bodies, the rule and its reasons: sq_compress_stage.inc):
+// k_further_compress above runs unchanged with the window table in place of `seg`, one wave per window
+__global__ __launch_bounds__(256) void k_fcw_tile_state(fcw::In G, int64_t ntiles, int32_t* state) {
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // one wave per tile
+    if (tile >= ntiles) return;
+    fcw::tile_state(G, tile, state);
+}
+__global__ __launch_bounds__(64) void k_fcw_tile_prefix(int64_t ntiles, const int32_t* state, int32_t* front) { fcw::tile_prefix(ntiles, state, front); }
+__global__ __launch_bounds__(256) void k_fcw_tile_flags(fcw::In G, int64_t ntiles, const int32_t* front, int32_t* flag) {
+    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= ntiles) return;
+    fcw::tile_flags(G, tile, front, flag);
+}
+__global__ __launch_bounds__(256) void k_fcw_scatter(int32_t n, const int32_t* flag, const int32_t* winc, int32_t* win) { fcw::scatter(n, flag, winc, win, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+struct FFcwIds { const int32_t *win, *merge; __device__ int operator()(int64_t w) const { return fcw::window_ids(win, merge, w); } };
+__global__ __launch_bounds__(256) void k_fcw_add(int32_t n, const int32_t* winc, const int32_t* off, int32_t* merge) { fcw::add_offsets(n, winc, off, merge, (int64_t)blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_fcw_longest(int32_t nwin, const int32_t* win, int32_t* longest) {  // (a timer row, nothing else reads it)
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    int x = w < nwin ? win[w + 1] - win[w] : 0;
+    for (int d = 32; d >= 1; d >>= 1) { const int o = __shfl_xor(x, d, 64); x = o > x ? o : x; }
+    if ((threadIdx.x & 63) == 0 && x > 0) atomicMax(longest, x);
+}
 // output nodes of FurtherCompressNode: one per run of equal merge ids; Support / AvgDepth reset (ledger B15)
 struct FMergeHead { const int32_t* merge; __device__ int operator()(int64_t i) const { return (i == 0 || merge[i] != merge[i - 1]) ? 1 : 0; } };
 __global__ void k_fc_gather(GNodes N, const int32_t* merge, const int32_t* newid, int32_t* remap, int32_t* o_chr, int32_t* o_pos, int32_t* o_len, int32_t* flags) {
@@ -918,6 +940,62 @@ int dev_compress_nodes(sq_ctx* c) {
     return SQ_OK;
 }
 
+// The window table of sq_compress_windows_on_device for the n nodes whose summary is in hasdisc / maxfar: win[0 .. nwin] and the inclusive
+// sum of the flags winc[0 .. n) inside D.fc_seg, with `extra` ints behind them for the caller.  Waits for the stream once: the walk's grid is nwin.
+static int fc_cut_windows(sq_ctx* c, const GraphUp& g, const int32_t* hasdisc, const int32_t* maxfar, size_t extra, int& nwin, int32_t*& win, int32_t*& winc, int32_t*& rest) {
+    DeviceRecords& D = *c->dev;
+    hipStream_t s = c->stream;
+    const int n = g.n;
+    const int64_t ntiles = ((int64_t)n + fcw::TILE - 1) / fcw::TILE;
+    HIPCHK(D.fc_seg.reserve(3 * (size_t)n + 1 + 4 * (size_t)ntiles + extra + 16));
+    win = D.fc_seg.p; winc = win + n + 1;
+    int32_t *flag = winc + n, *state = flag + n, *front = state + 2 * ntiles;
+    rest = front + 2 * ntiles;
+    int32_t* tot = D.flags.p + 9;
+    const fcw::In G{n, g.nchr, hasdisc, maxfar};
+    const dim3 tgrid((unsigned)((ntiles + 3) / 4));
+    {
+        EvTimer t(c, "k_fc_cuts", 0);
+        hipLaunchKernelGGL(k_fcw_tile_state, tgrid, dim3(256), 0, s, G, ntiles, state);
+        hipLaunchKernelGGL(k_fcw_tile_prefix, dim3(1), dim3(64), 0, s, ntiles, state, front);
+        hipLaunchKernelGGL(k_fcw_tile_flags, tgrid, dim3(256), 0, s, G, ntiles, front, flag);
+        HIPCHK((device_scan<OpSum, false>(s, n, FArr{flag}, winc, D.spine, tot)));
+        hipLaunchKernelGGL(k_fcw_scatter, grid_for(n, 256), dim3(256), 0, s, n, flag, winc, win);
+    }
+    int32_t h = 0;
+    HIPCHK(hipMemcpyAsync(&h, tot, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h < 1 || h > n) return fail(c, SQ_E_ARG, "internal: the window table of FurtherCompressNode holds " + std::to_string(h) + " windows for " + std::to_string(n) + " nodes");
+    nwin = h;
+    return SQ_OK;
+}
+
+// (tests: sq_debug_fc_windows) c->nodes / c->edges as they enter FurtherCompressNode -> the window table alone
+int dev_fc_windows_debug(sq_ctx* c, std::vector<int32_t>& table) {
+    table.clear();
+    const int n = (int)c->nodes.size(), m = (int)c->edges.size();
+    if (!n) return SQ_OK;
+    hipStream_t s = c->stream;
+    DeviceRecords& D = *c->dev;
+    GraphUp g;
+    int rc = graph_upload(c, g, true);
+    if (rc) return rc;
+    HIPCHK(D.g_x.reserve(6 * (size_t)n + 2 * (size_t)m + 16));
+    int32_t *off = nullptr, *inc = nullptr;
+    rc = graph_csr(c, g, D.g_x.p, off, inc, true);
+    if (rc) return rc;
+    int32_t *hasdisc = g.iscratch, *maxfar = hasdisc + n;
+    hipLaunchKernelGGL(k_fc_summary, grid_for(n, 256), dim3(256), 0, s, n, g.ea, g.eb, g.disc, off, inc, hasdisc, maxfar);
+    int nwin = 0;
+    int32_t *win = nullptr, *winc = nullptr, *rest = nullptr;
+    rc = fc_cut_windows(c, g, hasdisc, maxfar, 0, nwin, win, winc, rest);
+    if (rc) return rc;
+    table.resize((size_t)nwin + 1);
+    HIPCHK(hipMemcpyAsync(table.data(), win, table.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return SQ_OK;
+}
+
 // FurtherCompressNode (:2693-2892).  Returns 2 when a per-node edge list exceeded the kernel's capacity (caller: host version).
 int dev_further_compress(sq_ctx* c) {
     std::vector<Node>& N = c->nodes;
@@ -934,12 +1012,24 @@ int dev_further_compress(sq_ctx* c) {
     int32_t* tot = D.flags.p + 8;
     HIPCHK(hipMemsetAsync(merge, 0xff, (size_t)n * 4, s));
     HIPCHK(hipMemsetAsync(D.flags.p, 0, 4, s));
+    int fc_nwin = 0;  // (sq_compress_windows_on_device: the windows walked; 0: one walk per chromosome)
     {
         EvTimer t(c, "k_further_compress", 0);
         rc = graph_csr(c, g, D.g_x.p, off, inc, true);
         if (rc) return rc;
         int32_t *hasdisc = o, *maxfar = o + n;  // (the output area is written after the walk)
         hipLaunchKernelGGL(k_fc_summary, grid_for(n, 256), dim3(256), 0, s, n, g.ea, g.eb, g.disc, off, inc, hasdisc, maxfar);
+        if (c->fc_windows_on() && n) {
+            // one walk per independent window: the cut flags, the window table, the same walk over nwin waves, the ids in front of every window
+            int32_t *win = nullptr, *winc = nullptr, *woff = nullptr;
+            rc = fc_cut_windows(c, g, hasdisc, maxfar, (size_t)n + 1, fc_nwin, win, winc, woff);
+            if (rc) return rc;
+            HIPCHK(hipMemsetAsync(D.flags.p + 10, 0, 4, s));
+            hipLaunchKernelGGL(k_further_compress, dim3(fc_nwin), dim3(64), 0, s, g.nodes(), m, g.ea, g.eb, g.eh, g.disc, off, inc, c->P.concord_dist_idx, hasdisc, maxfar, merge, D.flags.p, win);
+            HIPCHK((device_scan<OpSum, true>(s, fc_nwin, FFcwIds{win, merge}, woff, D.spine, (int32_t*)nullptr)));
+            hipLaunchKernelGGL(k_fcw_add, grid_for(n, 256), dim3(256), 0, s, n, winc, woff, merge);
+            hipLaunchKernelGGL(k_fcw_longest, grid_for(fc_nwin, 256), dim3(256), 0, s, fc_nwin, win, D.flags.p + 10);
+        } else {
         // one walk per chromosome (run of equal Chr in the node list)
         std::vector<int32_t> seg;
         for (int i = 0; i < n; ++i) if (i == 0 || N[i].chr != N[i - 1].chr) seg.push_back(i);
@@ -954,16 +1044,19 @@ int dev_further_compress(sq_ctx* c) {
             hipLaunchKernelGGL(k_fc_addoff, grid_for(n, 256), dim3(256), 0, s, n, nseg, D.fc_seg.p, segoff, merge);
         }
         HIPCHK(hipStreamSynchronize(s));  // (`seg` goes out of scope)
+        }
         HIPCHK((device_scan<OpSum, true>(s, n, FMergeHead{merge}, newid, D.spine, tot)));
         hipLaunchKernelGGL(k_fc_gather, grid_for(n, 256), dim3(256), 0, s, g.nodes(), merge, newid, remap, o, o + n, o + 2 * (size_t)n, D.flags.p);
     }
-    int32_t n2 = 0, hf = 0;
+    int32_t n2 = 0, hf = 0, fc_longest = 0;
     HIPCHK(hipMemcpyAsync(&n2, tot, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(&hf, D.flags.p, 4, hipMemcpyDeviceToHost, s));
+    if (fc_nwin) HIPCHK(hipMemcpyAsync(&fc_longest, D.flags.p + 10, 4, hipMemcpyDeviceToHost, s));
     std::vector<int32_t> ho(3 * (size_t)n), hm(n);
     HIPCHK(hipMemcpyAsync(ho.data(), o, ho.size() * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(hm.data(), remap, (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (fc_nwin) { c->timer.add("fc_windows", 0.0, 0.0, fc_nwin); c->timer.add("fc_longest_window", 0.0, 0.0, fc_longest); }
     if (hf & (2 | 8)) return 2;
     if (hf & 4) return fail(c, SQ_E_ASSERT, "node merge map is not contiguous (the reference asserts at SegmentGraph.cpp:2862)");
     std::vector<Node> out((size_t)n2);

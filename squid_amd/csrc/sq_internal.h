@@ -280,6 +280,11 @@ struct sq_ctx {
     bool seg_dev_asked = false;
     int seg_dev_env = -1;
     bool seg_dev_on() const { return !bwa && !shard.on && (seg_dev_env >= 0 ? seg_dev_env != 0 : seg_dev_asked); }
+    // FurtherCompressNode's walk over independent windows instead of chromosomes (sq_compress_windows_on_device; SQUID_COMPRESS_WINDOWS_GPU=1 / =0,
+    // read by sq_create, forces / forbids it).  The stage is the same code for STAR, --bwa and sharded contexts, so all of them look at it
+    bool fc_windows_asked = false;
+    int fc_windows_env = -1;
+    bool fc_windows_on() const { return fc_windows_env >= 0 ? fc_windows_env != 0 : fc_windows_asked; }
     // --bwa: node depth and breakpoint support on the device (sq_bwa_on_device; SQUID_BWA_STAGES_GPU=1 / =0, read by sq_create, forces / forbids it)
     bool bwa_dev_asked = false;       // what the call said
     int bwa_dev_env = -1;             // the override: -1 none
@@ -586,6 +591,7 @@ int dev_filter_by_interleaving(sq_ctx* c, std::vector<uint8_t>& keep);
 int dev_filter_edges(sq_ctx* c, const std::vector<uint8_t>& keep);
 int dev_compress_nodes(sq_ctx* c);
 int dev_further_compress(sq_ctx* c);  // 2: capacity exceeded, take the host version
+int dev_fc_windows_debug(sq_ctx* c, std::vector<int32_t>& table);  // (sq_debug_fc_windows) the window table of sq_compress_windows_on_device for c->nodes / c->edges
 // RawEdgesChim / ExactBreakpoint + CountTop on the device (sq_chim_stage.inc).  fallback: the stage has more soft fragments than the bound
 // (SQUID_CHIM_SOFT_MAX, default 2^20) and nothing was done -- the caller takes the host route
 int dev_chimeric_edges(sq_ctx* c, std::vector<Edge>& raw, bool& fallback);

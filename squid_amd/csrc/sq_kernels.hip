@@ -39,6 +39,7 @@
 #include "sq_bwa_edges.inc"
 #include "sq_bwa_nodes.inc"
 #include "sq_segment_stage.inc"
+#include "sq_compress_stage.inc"
 
 #define HIPCHK(call)                                                                                         \
     do {                                                                                                     \
